@@ -18,6 +18,15 @@ torch.distributed (RCCL) is used only for the barriers around the timed region
 and the max-over-ranks of the elapsed time.
 
 Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the --steps steps and prints the headline line
+(metric, value, unit, ms_per_step, config, roofline.achieved / frac from ms_per_step).
+--full adds everything else, as one report:
+the analytic check of the timed output, HIP-event and per-launch times, the roofline
+(device copy / stream yardsticks, live PMC traffic), the fp64 secondary line and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step computed (rank 0's shard)
+as .npy files, see dump_outputs(); the inputs are closed-form, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -298,7 +307,7 @@ def live_pmc_traffic(workload, kernel_substr):
         d = tempfile.mkdtemp(prefix="fft_pmc_", dir="/tmp")
         try:
             cmd = [tool, "--pmc", cset, "-d", d, "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--workload", workload, "--steps", "3", "--warmup", "1", "--no-check", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic"]
+                   "--workload", workload, "--steps", "3", "--warmup", "1", "--full", "--no-check", "--no-cpu-baseline", "--no-secondary", "--no-live-traffic"]
             env = dict(os.environ)
             env["TMPDIR"] = "/tmp"
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
@@ -335,6 +344,27 @@ def device_copy_gbs(torch, x, y, iters=10):
     return 2.0 * x.numel() * x.element_size() / (best * 1e-3) / 1e9
 
 
+DUMP_ROW_BYTES = 48 << 20  # whole transforms in the dump; with the per-transform norms the files stay below 64 MB
+
+
+def dump_outputs(out_dir, torch, np, y):
+    """What the last timed step computed (y: this rank's [batch, n] output), as out_dir/<name>.npy:
+    output_rows.npy       whole transforms [k, n, 2] (re, im), float32 for f32 / float64 for f64: the rows of a fixed,
+                          seeded sample of the batch, as many as fit in DUMP_ROW_BYTES
+    output_row_index.npy  their indices in the batch (float64)
+    output_row_norms.npy  the L2 norm of every transform of the batch (float64), so that no transform goes uncompared"""
+    batch, n = y.shape
+    k = max(1, min(batch, DUMP_ROW_BYTES // (n * y.element_size())))
+    rows = np.sort(np.random.default_rng(0).choice(batch, size=k, replace=False))
+    sample = torch.view_as_real(y.index_select(0, torch.from_numpy(rows).to(y.device))).cpu().numpy()
+    slab = max(1, (1 << 24) // n)
+    norms = torch.cat([torch.linalg.vector_norm(y[s:s + slab].to(torch.complex128), dim=1) for s in range(0, batch, slab)])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output_rows.npy"), sample)
+    np.save(os.path.join(out_dir, "output_row_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "output_row_norms.npy"), norms.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -351,10 +381,17 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the fp64 2^19 secondary line and the device copy")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic live (two rocprofv3 --pmc child runs of this command); use profiles/pmc_traffic.json")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the result check, HIP-event / per-launch times, roofline (device copy, stream "
+                         "yardsticks, live PMC traffic), the fp64 secondary line and the CPU baseline (the --no-* switches apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) print the CPU baseline JSON for --workload and exit")
     ap.add_argument("--dry-run", action="store_true",
                     help="(tests) launcher rehearsal without a GPU: the ranks meet over gloo, reduce a dummy time and rank 0 prints n_gpus")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:  # child process of the main run: a crash here (e.g. SIGILL in a comparator) cannot lose the GPU line
         n, batch, dtype, desc = WORKLOADS[args.workload]
         print(json.dumps(cpu_baseline(n, dtype)), flush=True)
@@ -438,7 +475,7 @@ def main():
 
     # ---- correctness of what is being timed: analytic spectrum of every transform (first execute)
     check = {}
-    if not args.no_check:
+    if args.full and not args.no_check:
         src = x.clone() if args.inplace else x
         step()
         torch.cuda.synchronize()
@@ -486,97 +523,22 @@ def main():
     if dist:
         elapsed = reduce_max_seconds(dist, elapsed, device)
 
-    # ---- device-side duration of the same K steps, HIP events on the stream the kernels run on
-    ev_ms = plan.timed(x.data_ptr(), y.data_ptr(), args.steps)
-    torch.cuda.synchronize()
-    # per-step device times (one HIP-event pair per step): median and min next to the mean of the timed region
-    step_ms = sorted(plan.timed(x.data_ptr(), y.data_ptr(), 1) for _ in range(max(5, min(args.steps, 50))))
-    torch.cuda.synchronize()
+    ms_per_step = elapsed / args.steps * 1e3
+    value = float(n) * batch * world / (elapsed / args.steps) / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, y)
+
     # which schedule ran?  0: the one-round-trip team kernel (fft_team.h) did the work; 1: its XCD teams could not be
     # formed and the multi-pass fallback queued behind it did; -1: the plan has no team kernel (multi-pass schedule)
     team_status = plan.team_status()
     team = info.team_tiles > 0 and team_status == 0
     team_kernel_name = {1: "team_fft_kernel", 2: "team_defer_kernel", 3: "team_quad_kernel"}.get(info.team_kernel) if team else None
-    # ---- per-launch kernel durations, one more execute with a HIP event after every launch
-    per_pass = []
-    if not info.bluestein_m:
-        prof = [plan.profile_passes(x.data_ptr(), y.data_ptr(), 6) for _ in range(3)][-1]
-        team_name = {1: "team_fft_kernel", 2: "team_defer_kernel", 3: "team_quad_kernel"}.get(info.team_kernel, "team kernel")
-        names = ([team_name] + ["fallback pass %d (returns at once)" % i for i in range(8)]) if team else \
-                ["tile_fft_kernel pass %d" % i for i in range(8)]
-        per_pass = [{"pass": i, "kernel": names[i], "launches_per_step": c, "avg_launch_ms": m / c, "ms_per_step": m}
-                    for i, (m, c) in enumerate(prof)]
-    torch.cuda.synchronize()
-
-    points_per_step = float(n) * batch * world
     bytes_alg_per_step_gpu = 2.0 * n * batch * esz  # read every input once + write every output once
-    ms_per_step = elapsed / args.steps * 1e3
-    value = points_per_step / (elapsed / args.steps) / 1e9
-    ev_ms_per_step = ev_ms / args.steps
-    achieved = bytes_alg_per_step_gpu / (ev_ms_per_step * 1e-3) / 1e9
-    n_groups = -(-batch // max(1, info.chunk_batch)) if info.n_passes > 1 else 1
-    if info.bluestein_m:  # two transforms of length m per group; fused: 1 no element-wise kernels, 2 and the middle two passes as one
-        launches = ((2 * max(1, info.n_passes) - (1 if info.fused == 2 else 0)) * n_groups) + (0 if info.fused else 3)
-    else:
-        launches = info.n_passes * n_groups
-    units_per_launch = min(batch, info.chunk_batch) if info.n_passes > 1 else batch
-    if team:
-        # ONE team_fft_kernel launch carries the whole batch: every transform is read from HBM once and written once
-        # (the four-step transposition stays inside the XCDs), so the launch's own duration is the roofline denominator
-        n_groups, units_per_launch = 1, batch
-        team_ms = per_pass[0]["avg_launch_ms"] if per_pass else ev_ms_per_step
-        achieved = bytes_alg_per_step_gpu / (team_ms * 1e-3) / 1e9
-        tile_points = 8192 if dtype == "f32" else 4096  # one 64 KiB tile
-        team_cus = max(1, n // (info.team_tiles * tile_points))
-        team_src = {1: "csrc/fft_team.h team_fft_kernel", 2: "csrc/fft_team_defer.h team_defer_kernel",
-                    3: "csrc/fft_team_quad.h team_quad_kernel (256-byte row segments, both steps decimated in time by 4, the "
-                       "exchange between them in four rounds through the XCD's L2; n = 2^18 ... 2^20: one image per seat in the window, per-seat counters)"}.get(info.team_kernel, "team kernel")
-        kernel_desc = ("%s: ONE launch per step transforms all %d transforms, a whole transform per team of "
-                       "%d CUs of one XCD (256 workgroups = %d teams, %d 64 KiB tiles per workgroup and step); the %d multi-pass launches "
-                       "queued behind it as its fallback return at once" % (team_src, batch, team_cus, 256 // team_cus, info.team_tiles, launches))
-    else:
-        kernel_desc = ("tile_fft_kernel: one launch per pass per group of %d transforms (%d launches per step); the "
-                       "dominant unit of work is the launch SET that carries a group through all %d passes"
-                       % (units_per_launch, launches, max(1, info.n_passes)))
-        if info.bluestein_m:
-            kernel_desc += ("; Bluestein = forward + inverse transform of length %d with the chirp / spectral products fused into "
-                            "their first load and last store%s" % (info.bluestein_m, ", the forward's last pass and the inverse's first "
-                            "as ONE kernel (tile_fft_ba_kernel)" if info.fused == 2 else ""))
-
     achieved_wall = bytes_alg_per_step_gpu / (ms_per_step * 1e-3) / 1e9
-    # HBM traffic from the PMC counters comes from separate rocprofv3 --pmc runs (never combined with tracing);
-    # the committed summary is attached when it was taken on this same workload / plan shape.
-    traffic, traffic_note = None, "collected by separate rocprofv3 --pmc runs, see profiles/"
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-            pt = json.load(f)
-        ent = pt.get(args.workload + ("_team" if team else ""))
-        if ent and ent.get("factors") == [v for v in info.factors if v] and ent.get("units_per_launch") == units_per_launch:
-            if ent.get("kernel_source_hash") == kernel_source_hash():
-                traffic = ent["hbm_bytes_per_launch_set"]
-                traffic_note = ent["note"]
-            else:
-                traffic_note = ("profiles/pmc_traffic.json holds a figure for this workload, taken on other kernel sources (hash %s, now %s): "
-                                "not attached; re-run tools/profile_round.sh" % (ent.get("kernel_source_hash"), kernel_source_hash()))
-    except Exception:
-        pass
-
-    traffic_source = "profiles/pmc_traffic.json (committed rocprofv3 --pmc summary, same kernel sources)" if traffic is not None else None
-    traffic_committed = traffic
-    if rank == 0 and world == 1 and team and team_kernel_name and not args.no_live_traffic:
-        live = live_pmc_traffic(args.workload, team_kernel_name)
-        if live:
-            traffic = live[0]
-            traffic_source = "live: two rocprofv3 --pmc child runs of this command (FETCH_SIZE x 2 + WRITE_SIZE, average per launch of %s)" % team_kernel_name
-            traffic_note = ("measured in this run: reads %.2f GB, writes %.2f GB per launch against %.2f GB algorithmic = %.2f x; committed summary: %s"
-                            % (live[1] / 1e9, live[2] / 1e9, 2.0 * n * esz * units_per_launch / 1e9, live[0] / (2.0 * n * esz * units_per_launch),
-                               ("%.2f GB" % (traffic_committed / 1e9)) if traffic_committed else "none for these sources"))
-
     result = {
         "metric": "Gpoint/s + achieved HBM GB/s, batched 1D c2c FFT at 1/2/4/8 MI355X",
         "value": value, "unit": "Gpoint/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "ms_per_step_median": step_ms[len(step_ms) // 2], "ms_per_step_min": step_ms[0],
-        "value_median": float(n) * batch * world / (step_ms[len(step_ms) // 2] * 1e-3) / 1e9,
+        "ms_per_step": ms_per_step,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": dtype, "data": "synthetic",
         "achieved_hbm_gbs": 2.0 * n * batch * world * esz / (elapsed / args.steps) / 1e9,
@@ -591,11 +553,93 @@ def main():
             "team_tiles": info.team_tiles, "team_status": team_status,
             "device": lib.fft_gpu_get_device_name().decode(),
         },
-        "roofline": {
-            # achieved / frac: from ms_per_step, the wall clock of the timed region (what the driver can check against its own clock);
+        # achieved / frac: from ms_per_step, the wall clock of the timed region (what the driver can check against its own clock);
+        # --full adds the kernel-time figures, the traffic and the yardsticks
+        "roofline": {"bound": "hbm", "achieved": achieved_wall, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved_wall / HBM_PEAK_GBS},
+    }
+    if args.full:
+        # ---- device-side duration of the same K steps, HIP events on the stream the kernels run on
+        ev_ms = plan.timed(x.data_ptr(), y.data_ptr(), args.steps)
+        torch.cuda.synchronize()
+        # per-step device times (one HIP-event pair per step): median and min next to the mean of the timed region
+        step_ms = sorted(plan.timed(x.data_ptr(), y.data_ptr(), 1) for _ in range(max(5, min(args.steps, 50))))
+        torch.cuda.synchronize()
+        # ---- per-launch kernel durations, one more execute with a HIP event after every launch
+        per_pass = []
+        if not info.bluestein_m:
+            prof = [plan.profile_passes(x.data_ptr(), y.data_ptr(), 6) for _ in range(3)][-1]
+            team_name = {1: "team_fft_kernel", 2: "team_defer_kernel", 3: "team_quad_kernel"}.get(info.team_kernel, "team kernel")
+            names = ([team_name] + ["fallback pass %d (returns at once)" % i for i in range(8)]) if team else \
+                    ["tile_fft_kernel pass %d" % i for i in range(8)]
+            per_pass = [{"pass": i, "kernel": names[i], "launches_per_step": c, "avg_launch_ms": m / c, "ms_per_step": m}
+                        for i, (m, c) in enumerate(prof)]
+        torch.cuda.synchronize()
+
+        ev_ms_per_step = ev_ms / args.steps
+        achieved = bytes_alg_per_step_gpu / (ev_ms_per_step * 1e-3) / 1e9
+        n_groups = -(-batch // max(1, info.chunk_batch)) if info.n_passes > 1 else 1
+        if info.bluestein_m:  # two transforms of length m per group; fused: 1 no element-wise kernels, 2 and the middle two passes as one
+            launches = ((2 * max(1, info.n_passes) - (1 if info.fused == 2 else 0)) * n_groups) + (0 if info.fused else 3)
+        else:
+            launches = info.n_passes * n_groups
+        units_per_launch = min(batch, info.chunk_batch) if info.n_passes > 1 else batch
+        if team:
+            # ONE team_fft_kernel launch carries the whole batch: every transform is read from HBM once and written once
+            # (the four-step transposition stays inside the XCDs), so the launch's own duration is the roofline denominator
+            n_groups, units_per_launch = 1, batch
+            team_ms = per_pass[0]["avg_launch_ms"] if per_pass else ev_ms_per_step
+            achieved = bytes_alg_per_step_gpu / (team_ms * 1e-3) / 1e9
+            tile_points = 8192 if dtype == "f32" else 4096  # one 64 KiB tile
+            team_cus = max(1, n // (info.team_tiles * tile_points))
+            team_src = {1: "csrc/fft_team.h team_fft_kernel", 2: "csrc/fft_team_defer.h team_defer_kernel",
+                        3: "csrc/fft_team_quad.h team_quad_kernel (256-byte row segments, both steps decimated in time by 4, the "
+                           "exchange between them in four rounds through the XCD's L2; n = 2^18 ... 2^20: one image per seat in the window, per-seat counters)"}.get(info.team_kernel, "team kernel")
+            kernel_desc = ("%s: ONE launch per step transforms all %d transforms, a whole transform per team of "
+                           "%d CUs of one XCD (256 workgroups = %d teams, %d 64 KiB tiles per workgroup and step); the %d multi-pass launches "
+                           "queued behind it as its fallback return at once" % (team_src, batch, team_cus, 256 // team_cus, info.team_tiles, launches))
+        else:
+            kernel_desc = ("tile_fft_kernel: one launch per pass per group of %d transforms (%d launches per step); the "
+                           "dominant unit of work is the launch SET that carries a group through all %d passes"
+                           % (units_per_launch, launches, max(1, info.n_passes)))
+            if info.bluestein_m:
+                kernel_desc += ("; Bluestein = forward + inverse transform of length %d with the chirp / spectral products fused into "
+                                "their first load and last store%s" % (info.bluestein_m, ", the forward's last pass and the inverse's first "
+                                "as ONE kernel (tile_fft_ba_kernel)" if info.fused == 2 else ""))
+
+        # HBM traffic from the PMC counters comes from separate rocprofv3 --pmc runs (never combined with tracing);
+        # the committed summary is attached when it was taken on this same workload / plan shape.
+        traffic, traffic_note = None, "collected by separate rocprofv3 --pmc runs, see profiles/"
+        try:
+            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                pt = json.load(f)
+            ent = pt.get(args.workload + ("_team" if team else ""))
+            if ent and ent.get("factors") == [v for v in info.factors if v] and ent.get("units_per_launch") == units_per_launch:
+                if ent.get("kernel_source_hash") == kernel_source_hash():
+                    traffic = ent["hbm_bytes_per_launch_set"]
+                    traffic_note = ent["note"]
+                else:
+                    traffic_note = ("profiles/pmc_traffic.json holds a figure for this workload, taken on other kernel sources (hash %s, now %s): "
+                                    "not attached; re-run tools/profile_round.sh" % (ent.get("kernel_source_hash"), kernel_source_hash()))
+        except Exception:
+            pass
+
+        traffic_source = "profiles/pmc_traffic.json (committed rocprofv3 --pmc summary, same kernel sources)" if traffic is not None else None
+        traffic_committed = traffic
+        if rank == 0 and world == 1 and team and team_kernel_name and not args.no_live_traffic:
+            live = live_pmc_traffic(args.workload, team_kernel_name)
+            if live:
+                traffic = live[0]
+                traffic_source = "live: two rocprofv3 --pmc child runs of this command (FETCH_SIZE x 2 + WRITE_SIZE, average per launch of %s)" % team_kernel_name
+                traffic_note = ("measured in this run: reads %.2f GB, writes %.2f GB per launch against %.2f GB algorithmic = %.2f x; committed summary: %s"
+                                % (live[1] / 1e9, live[2] / 1e9, 2.0 * n * esz * units_per_launch / 1e9, live[0] / (2.0 * n * esz * units_per_launch),
+                                   ("%.2f GB" % (traffic_committed / 1e9)) if traffic_committed else "none for these sources"))
+
+        result["ms_per_step_median"] = step_ms[len(step_ms) // 2]
+        result["ms_per_step_min"] = step_ms[0]
+        result["value_median"] = float(n) * batch * world / (step_ms[len(step_ms) // 2] * 1e-3) / 1e9
+        result["roofline"].update({
             # achieved_kernel / frac_kernel: from the dominant kernel's own HIP-event time (the figure rocprofv3's average must agree with)
-            "bound": "hbm", "achieved": achieved_wall, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved_wall / HBM_PEAK_GBS, "achieved_kernel": achieved, "frac_kernel": achieved / HBM_PEAK_GBS,
+            "achieved_kernel": achieved, "frac_kernel": achieved / HBM_PEAK_GBS,
             "traffic": traffic, "traffic_source": traffic_source,
             "traffic_over_algorithmic": (traffic / (2.0 * n * esz * units_per_launch)) if traffic else None,
             "dominant_kernel": team_kernel_name if team else ("tile_fft_ba_kernel + tile_fft_kernel" if info.bluestein_m else
@@ -611,10 +655,9 @@ def main():
                     "share); achieved_kernel = the same bytes per launch set / HIP-event duration of the set (events on the plan's stream; team "
                     "schedule: of the team kernel's launch alone); per_pass = live HIP-event time of each launch; "
                     "traffic: " + traffic_note,
-        },
-        "check": check,
-    }
-    if not args.no_secondary:
+        })
+        result["check"] = check
+    if args.full and not args.no_secondary:
         # the practical ceiling on this box, and an fp64 line (N = 2^19 is the largest fp64 team-kernel size)
         try:
             copy_torch = device_copy_gbs(torch, x, y if not args.inplace else torch.empty_like(x))
@@ -655,7 +698,7 @@ def main():
                 del x2, y2
             except Exception as e:
                 result["secondary_fp64"] = {"value": None, "note": "failed: %r" % (e,)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # in a child process: the comparators load CPU libraries built on another host; whatever happens to them, the
         # GPU line below is printed
         try:

@@ -127,6 +127,12 @@ def ref(fast=False):
     return _ref
 
 
+def digest(x):
+    """SHA-256 of a complex128 array's bytes, as uint8[32]: how tests/golden/ stores outputs too large to keep whole."""
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(x, dtype=np.complex128).tobytes()).digest(), dtype=np.uint8)
+
+
 def ref_fft(x, direction=FFT_FORWARD, algo="dit", lib=None):
     """Run the REAL reference routine (in place semantic, returns a copy)."""
     lib = lib or ref()

@@ -10,9 +10,8 @@ timeout -k 10 900 python3 tools/quad_soak.py 250 > gpurun_out/r4_quad_soak.txt 2
 tail -12 gpurun_out/r4_quad_soak.txt
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r4_smoke.txt 2>&1 || { tail -5 gpurun_out/r4_smoke.txt; exit 1; }
 tail -1 gpurun_out/r4_smoke.txt
-timeout -k 10 600 python3 bench.py > gpurun_out/r4_bench_default.json 2> gpurun_out/r4_bench_default.err || { tail -5 gpurun_out/r4_bench_default.err; exit 1; }
-python3 -c "
-import json
-d=json.loads(open('gpurun_out/r4_bench_default.json').read().strip().splitlines()[-1])
+timeout -k 10 600 python3 bench.py --full | python3 -c "
+import json,sys
+d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']
-print('bench: value %.1f Gpoint/s ms_per_step %.3f frac %.3f frac_kernel %.3f traffic_over_algorithmic %s (%s) secondary %s cpu %s' % (d['value'], d['ms_per_step'], r['frac'], r['frac_kernel'], r['traffic_over_algorithmic'], r.get('traffic_source'), d['secondary_fp64']['value'], d['cpu_baseline']['value']))"
+print('bench: value %.1f Gpoint/s ms_per_step %.3f frac %.3f frac_kernel %.3f traffic_over_algorithmic %s (%s) secondary %s cpu %s' % (d['value'], d['ms_per_step'], r['frac'], r['frac_kernel'], r['traffic_over_algorithmic'], r.get('traffic_source'), d['secondary_fp64']['value'], d['cpu_baseline']['value']))" || exit 1

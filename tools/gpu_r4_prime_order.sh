@@ -11,7 +11,7 @@ for rep in 1 2; do
 for ab in "-1 0" "32 0" "-1 32" "32 32" "8 8" "64 64"; do
   set -- $ab
   echo "## ORDER_A=$1 ORDER_B=$2"
-  FFT_HIP_ORDER_A=$1 FFT_HIP_ORDER_B=$2 timeout -k 10 200 python3 bench.py --workload prime --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-live-traffic 2>/dev/null | python3 -c "
+  FFT_HIP_ORDER_A=$1 FFT_HIP_ORDER_B=$2 timeout -k 10 200 python3 bench.py --full --workload prime --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-live-traffic 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value %.2f Gpoint/s, %.3f ms/step, check %s' % (d['value'], d['ms_per_step'], d['check'].get('ok')))

@@ -26,6 +26,6 @@ done
 cd $R
 for wl in 1m 64k 256k prime 1k; do
   extra="--no-cpu-baseline"; [ $wl = 1m ] && extra=""
-  timeout -k 10 500 python3 bench.py --workload $wl --steps 20 --warmup 3 $extra > $O/bench_$wl.json 2> $O/bench_$wl.err || { echo "bench $wl failed"; tail -5 $O/bench_$wl.err; exit 1; }
+  timeout -k 10 500 python3 bench.py --full --workload $wl --steps 20 --warmup 3 $extra > $O/bench_$wl.json 2> $O/bench_$wl.err || { echo "bench $wl failed"; tail -5 $O/bench_$wl.err; exit 1; }
 done
 python3 tools/collect_profiles3.py $tag
