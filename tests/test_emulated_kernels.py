@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import emu_lib as E
+import accuracy as A
 import oracle_lib as O
 
 
@@ -185,6 +186,7 @@ def test_team_kernel(n, batch, dtype, log2seats, n_xcc, threads, lds, tiles, pla
                                      inplace=inplace, tiles=tiles)
             assert info[0] // 100 == tiles, "team kernel was not planned"
             assert rel(y, oracle(x, d)) < TEAM_TOL[dtype], (n, d, inplace)
+            A.check_rows(y, x, d, "team_defer", label="emulated team n=%d inplace=%d" % (n, inplace))  # every transform, bin by bin
 
 
 def test_wide_row_kernel(monkeypatch):
@@ -233,6 +235,7 @@ def test_team_quad_kernel(n, batch, log2seats, n_xcc, threads, lds, dtype, monke
             assert info[0] // 100 == 4 and info[6] & 8, "team_quad_kernel was not planned"
             assert info[5] == 1, "status / fallback / timeout counters: %d" % info[5]
             assert rel(y, oracle(x, d)) < TEAM_TOL[dtype], (n, batch, d, inplace)
+            A.check_rows(y, x, d, "team_quad", label="emulated quad n=%d inplace=%d" % (n, inplace))  # every transform, bin by bin
 
 
 def test_team_quad_kernel_with_deferred_result_stores(tmp_path):
@@ -248,7 +251,7 @@ def test_team_quad_kernel_with_deferred_result_stores(tmp_path):
     code = (
         "import sys, numpy as np\n"
         "sys.path.insert(0, %r)\n"
-        "import emu_lib as E, oracle_lib as O\n"
+        "import emu_lib as E, oracle_lib as O, accuracy as A\n"
         "import os; os.environ['FFT_EMU_TEAM_QUAD'] = '1'\n"
         "for n, batch, log2seats, n_xcc, threads, lds in %r:\n"
         "    x = O.gen_lcg(n, 23, batch).astype(np.complex64)\n"
@@ -260,6 +263,7 @@ def test_team_quad_kernel_with_deferred_result_stores(tmp_path):
         "            assert info[6] & 8 and info[5] == 1, (n, info[5])\n"
         "            err = np.linalg.norm(y - ref) / np.linalg.norm(ref)\n"
         "            assert err < 2e-6, (n, batch, dyn, inplace, err)\n"
+        "            A.check_rows(y, x, -1, 'team_quad', label='deferred stores n=%%d' %% n)\n"
         "print('ok')\n" % (os.path.dirname(os.path.abspath(__file__)), QUAD_CASES))
     env = dict(os.environ, FFT_EMU_SO=so)
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
@@ -279,6 +283,7 @@ def test_team_quad_kernel_static_and_dynamic_split_of_the_batch(monkeypatch):
             y, info = E.emu_fft_team(x, -1, log2seats=log2seats, n_xcc=n_xcc, threads=threads, lds_budget=lds)
             assert info[6] & 8 and info[5] == 1, (n, dyn, info[5])
             assert rel(y, oracle(x, -1)) < TEAM_TOL[np.complex64], (n, batch, dyn)
+            A.check_rows(y, x, -1, "team_quad", label="emulated quad dyn=%s" % dyn)
             res.append(y)
         assert np.array_equal(res[0], res[1])
 
@@ -305,6 +310,7 @@ def test_team_quad_kernel_pair_protocol(n, batch, log2seats, n_xcc, threads, lds
                 y, info = E.emu_fft_team(x, d, log2seats=log2seats, n_xcc=n_xcc, threads=threads, lds_budget=lds, inplace=inplace)
                 assert info[0] // 100 == 4 and info[6] & 8 and info[5] == 1, (n, dyn, info[5])
                 assert rel(y, oracle(x, d)) < TEAM_TOL[np.complex64], (n, batch, dyn, d, inplace)
+                A.check_rows(y, x, d, "team_quad", label="pair protocol dyn=%s inplace=%d" % (dyn, inplace))
                 if d == -1 and not inplace:
                     res.append(y)
     assert np.array_equal(res[0], res[1])
@@ -315,6 +321,7 @@ def test_team_quad_kernel_pair_protocol(n, batch, log2seats, n_xcc, threads, lds
         y, info = E.emu_fft_team(x, -1, log2seats=log2seats, n_xcc=n_xcc, threads=threads, lds_budget=lds)
         assert info[3] == 1100, "timeout seen, nothing lost: %d" % info[3]
         assert rel(y, oracle(x, -1)) < TEAM_TOL[np.complex64]
+        A.check_rows(y, x, -1, "team_quad", label="pair protocol after the repair")
 
 
 @pytest.mark.parametrize("quad", [False, True])

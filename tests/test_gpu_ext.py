@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import accuracy as A
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +101,9 @@ def test_r2c_c2r_vs_oracle(gpu_lib, n, batch, dtype):
     assert r <= TOL[np.dtype(dtype)] and r <= TIGHT[np.dtype(dtype)] * 4, (n, r)
     back = fftlib.irfft(X, n)
     assert np.linalg.norm(back - x) / np.linalg.norm(x) <= TIGHT[np.dtype(dtype)] * 8
+    # per transform, bin by bin: r2c against the float64 transform of x, c2r against the float64 inverse of the r2c result
+    A.check_rows(X, x, -1, "r2c", n=n, ref=lambda xs: np.fft.rfft(xs.astype(np.float64), axis=-1), label="r2c")
+    A.check_rows(back, X, 1, "r2c", n=n, ref=lambda Xs: np.fft.irfft(Xs.astype(np.complex128), n, axis=-1), label="c2r")
     assert rel(fftlib.irfft(ref.astype(X.dtype), n), O.oracle_c2r(ref, n)) <= TIGHT[np.dtype(dtype)] * 8
 
 
@@ -273,6 +277,9 @@ def test_bluestein_fused_equals_unfused_and_oracle(gpu_lib, n, batch, dtype):
             plan.execute_ptr(buf.ptr, buf.ptr)  # in place: the user's array is both the first load and the last store
             assert plan.sync() == 0
             res.append(buf.download(x.shape, dtype))
+        m = plan.info().bluestein_m
+        for v, r_v in enumerate(res):  # every transform of every variant against the float64 reference
+            A.check_rows(r_v, x, d, "bluestein", m=m, label="bluestein variant %d" % v)
         ref = O.oracle_fft(x[:1].astype(np.complex128), d, "bluestein")
         r = rel(res[0][:1], ref)
         # the reference's own error grows ~ n eps (twiddle recurrence, SURVEY.md fact 8: 2e-10 at n = 10^6): the oracle
@@ -443,6 +450,11 @@ def test_random_sizes_roundtrip_parseval_and_numpy(gpu_lib):
             e_f = np.sum(np.abs(X.astype(np.complex128)) ** 2, axis=1) / n
             assert np.max(np.abs(e_f - e_t) / e_t) < tol * 4, (n, batch, dtype)
             assert rel(X[:1], np.fft.fft(x[:1].astype(np.complex128), axis=1)) < tol, (n, batch, dtype)
+            # every transform, both directions, bin by bin (a permutation or a swap of transforms passes round trip + Parseval)
+            info = fwd.info()
+            fam = "bluestein" if info.bluestein_m else "wide_row" if (info.n_passes == 1 and n >= 8192) else "multipass"
+            A.check_rows(X, x, -1, fam, m=info.bluestein_m, label="random sizes")
+            A.check_rows(back, X, 1, fam, m=info.bluestein_m, label="random sizes inverse")
             fwd.destroy(); inv.destroy(); a.free(); b.free()
 
 
