@@ -1149,7 +1149,7 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     info->device = p->device;
     auto fill = [&](auto* core) {
         info->algo = core->algo;
-        info->chunk_batch = core->chunk;
+        info->chunk_batch = core->wide.ok ? core->max_batch : core->chunk;  // wide_row_kernel: the whole batch in one launch
         info->team_tiles = core->team.ok ? core->team.NT : 0;
         info->team_kernel = !core->team.ok ? 0 : core->team.quad ? 3 : core->team.defer ? 2 : 1;
         if (core->team.ok) info->workspace_bytes += core->team.scratch_bytes;
@@ -1159,6 +1159,9 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
             info->factors[0] = 1 << core->log2n;
         } else if (core->algo == ffteng::ALGO_RADIX2_GLOBAL) {
             info->n_passes = core->log2n + 1;
+        } else if (core->log2n == 0) {
+            info->n_passes = 1;  // n = 1: one scale-copy launch over the batch (none in place forward), no tile passes
+            info->factors[0] = 1;
         } else {
             info->n_passes = core->wide.ok ? 1 : (int)core->passes.size();
             for (size_t i = 0; i < core->passes.size() && i < 4; i++) info->factors[i] = 1 << core->passes[i].log2L;

@@ -42,8 +42,10 @@ U = {np.dtype(np.complex64): 2.0 ** -24, np.dtype(np.complex128): 2.0 ** -53,
 # K of the bound K * u * log2(n) per path family, and the worst e_b / (u * log2 n) measured on the MI355X over the GPU suite
 # (fp32 / fp64).  Each K is at least twice the worst measured value; caps: 16 for the power-of-two paths, 64 for Bluestein.
 BOUND_K = {
-    "multipass": 8,    # multi-pass and single-pass schedules (csrc/fft_kernels.h)       measured 0.94 (2^11) / 1.08 (2^6)
-    "wide_row": 9,     # wide_row_kernel: fp32 n = 8192, 16384, fp64 n = 8192              measured 4.21 / 1.25 (2^13)
+    "multipass": 8,    # multi-pass and single-pass schedules (csrc/fft_kernels.h)       measured 2.16 (2^4) / 2.58 (2^4)
+    "radix2_global": 8,  # bitrev_kernel + radix2_dit_stage_kernel, one launch per stage   measured 1.98 (2^6) / 2.06 (2^3)
+    "radix2_shfl": 8,    # wave_dit_kernel: one wavefront per transform, n = 128 ... 1024  measured 1.57 (2^9) / 2.18 (2^7)
+    "wide_row": 9,     # wide_row_kernel: fp32 n = 8192, 16384, fp64 n = 8192              measured 4.21 / 1.25 (2^13); fp32 2^13 x (2^18 + 1): 5.25, over K / 2 (open)
     "team_quad": 8,    # team_quad_kernel (csrc/fft_team_quad.h)                          measured 3.74 (2^20) / 2.18 (2^16)
     "team_defer": 8,   # team_defer_kernel / team_fft_kernel (csrc/fft_team*.h)          measured   -  / 1.91 (2^17); no fp32 size runs them
     "bluestein": 32,   # chirp-z over a power-of-two core of length m                     measured 1.81 (1000) / 2.41 (100003)
@@ -143,6 +145,35 @@ def normal_rows(n, b0, count, dtype, seed):
 
     with ThreadPoolExecutor(WORKERS) as ex:
         list(ex.map(one, range(count)))
+    return out
+
+
+BLOCK_BYTES = 2 << 20  # block_normal_rows draws its rows in blocks of about 2 MiB, one generator per block
+
+
+def block_rows(n, dtype):
+    """Rows per block of block_normal_rows (at least one)."""
+    return max(1, BLOCK_BYTES // (n * np.dtype(dtype).itemsize))
+
+
+def block_normal_rows(n, b0, count, dtype, seed):
+    """Rows b0 .. b0 + count - 1 of a batch of complex normal values drawn block by block: block j (rows j*R .. (j+1)*R - 1,
+    R = block_rows(n, dtype)) comes from default_rng((seed, j)).  Any row range can be regenerated on its own, neighbouring
+    transforms differ, and a batch of 2^27 rows needs only 2^27 / R generators (normal_rows makes one per row)."""
+    dt = np.dtype(dtype)
+    real = np.float32 if dt == np.dtype(np.complex64) else np.float64
+    R = block_rows(n, dt)
+    out = np.empty((count, n), dtype=dt)
+    if count == 0:
+        return out
+
+    def one(j):
+        lo, hi = max(b0, j * R), min(b0 + count, (j + 1) * R)
+        blk = np.random.default_rng((seed, j)).standard_normal(2 * n * (hi - j * R), dtype=real).view(dt).reshape(-1, n)
+        out[lo - b0:hi - b0] = blk[lo - j * R:]
+
+    with ThreadPoolExecutor(WORKERS) as ex:
+        list(ex.map(one, range(b0 // R, (b0 + count - 1) // R + 1)))
     return out
 
 
@@ -367,6 +398,76 @@ def same_bits(ga, gb, dtype, width):
             diff = np.flatnonzero(np.any(a.view(np.uint8).reshape(cnt, -1) != b.view(np.uint8).reshape(cnt, -1), axis=1))
             return r0 + int(diff[0])
     return None
+
+
+def check_execute_streamed(plan, n, batch, dtype, seed, family, direction=None, inplace=True, label="", expect=None, long_rows=0,
+                           exact=False):
+    """check_execute() for batches that do not fit the host: the input rows are block_normal_rows(n, ., ., dtype, seed), and
+    every transfer and check runs in slices of at most SLICE_BYTES of complex128 reference rows, so that host memory stays at a
+    few slices whatever the batch.  The same checks:
+      - the output is NaN-filled and sits between two guard rows, both intact afterwards;
+      - the input of the out-of-place execute is unchanged;
+      - every transform: e_b <= bound(family) (fp64 and long_rows > 0: the first rows also against a long-double reference);
+        exact=True: also every output word equal to the input word (n = 1);
+      - inplace=True: the in-place result (guarded too) bit-identical to the out-of-place one;
+      - expect() after each sync.
+    Returns the largest e_b of the out-of-place run."""
+    direction = plan.direction if direction is None else direction
+    dt = np.dtype(dtype)
+    rb = n * dt.itemsize
+    step = _slice_rows(16 * n)  # rows per slice: complex128 reference rows of at most SLICE_BYTES
+
+    def rows(r0, cnt):
+        return block_normal_rows(n, r0, cnt, dt, seed)
+
+    def upload(g):
+        for r0 in range(0, batch, step):
+            g.upload(rows(r0, min(step, batch - r0)), r0)
+
+    gin, gout = Guarded(batch, rb), Guarded(batch, rb)
+    gip = None
+    try:
+        upload(gin)
+        gout.fill(np.full(n, np.nan, dtype=dt))
+        plan.execute_ptr(gin.ptr, gout.ptr)
+        assert plan.sync() == 0, label
+        if expect:
+            expect()
+        assert gout.guards_intact(), "%s: out-of-place execute wrote outside [out, out + batch * n)" % label
+        assert gin.guards_intact(), "%s: out-of-place execute wrote next to its input" % label
+        worst = 0.0
+        for r0 in range(0, batch, step):
+            cnt = min(step, batch - r0)
+            x = rows(r0, cnt)
+            xd = gin.rows_at(r0, cnt, dt, n)
+            if not np.array_equal(xd.view(np.uint8), x.view(np.uint8)):
+                bad = int(np.flatnonzero(np.any(xd.view(np.uint8).reshape(cnt, -1) != x.view(np.uint8).reshape(cnt, -1), axis=1))[0])
+                raise AssertionError("%s: out-of-place execute changed its input (transform %d)" % (label, r0 + bad))
+            del xd
+            y = gout.rows_at(r0, cnt, dt, n)
+            if exact and not np.array_equal(y.view(np.uint8), x.view(np.uint8)):
+                bad = int(np.flatnonzero(np.any(y.view(np.uint8).reshape(cnt, -1) != x.view(np.uint8).reshape(cnt, -1), axis=1))[0])
+                raise AssertionError("%s: output differs from the input at transform %d" % (label, r0 + bad))
+            e = check_rows(y, x, direction, family, dt, n=n, label=label + " out-of-place", b0=r0, long_rows=long_rows if r0 == 0 else 0)
+            worst = max(worst, float(np.max(e)))
+            del x, y
+        gin.free()
+        gin = None
+        if inplace:
+            gip = Guarded(batch, rb)
+            upload(gip)
+            plan.execute_ptr(gip.ptr, gip.ptr)
+            assert plan.sync() == 0, label
+            if expect:
+                expect()
+            assert gip.guards_intact(), "%s: in-place execute wrote outside [buf, buf + batch * n)" % label
+            b = same_bits(gip, gout, dt, n)
+            assert b is None, "%s: in-place result differs from the out-of-place one at transform %d" % (label, b)
+        return worst
+    finally:
+        for g in (gin, gout, gip):
+            if g is not None:
+                g.free()
 
 
 def check_execute(plan, x, family, direction=None, inplace=True, m=None, label="", expect=None, long_rows=0, ref=None):

@@ -192,3 +192,108 @@ def test_two_tone_check_every_transform():
     bad[66, f] -= 3 * lim
     with pytest.raises(A.AccuracyError, match="worst transform 71 \\(bin %d" % f):
         A.check_two_tone(bad, 5, n, "multipass")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# check_execute_streamed on host memory, with SLICE_BYTES small enough that the batch spans four slices
+# ---------------------------------------------------------------------------------------------------------------------------
+STREAM_N, STREAM_BATCH, STREAM_SEED = 256, 1000, 21
+
+
+class StreamedPlan(NumpyPlan):
+    """A numpy plan on host memory; `defect` names one kind of wrong result or stray write."""
+
+    def execute_ptr(self, d_in, d_out):
+        mem = A.memory()
+        n, batch, rb = self.n, self.batch, self.n * self.dtype.itemsize
+        x = mem.d2h(d_in, (batch, n), self.dtype)
+        y = (np.fft.fft(x, axis=1) if self.direction < 0 else np.fft.ifft(x, axis=1)).astype(self.dtype)
+        step = A._slice_rows(16 * n)
+        if self.defect == "bin_last_slice":
+            b = batch - 2
+            y[b, 77] += 1e3 * A.bound("multipass", self.dtype, n) * np.sqrt(np.mean(np.abs(y[b]) ** 2))
+        elif self.defect == "swap_across_slices":
+            y[[step - 1, step]] = y[[step, step - 1]]
+        elif self.defect == "wrapped_index":
+            w = np.empty_like(y)
+            w[:] = np.nan
+            for b in range(batch):
+                w[b % 512] = y[b]  # transform b written at row b mod 2^9: an index that wraps, scaled down from 2^31
+            y = w if d_in != d_out else np.where(np.isnan(w), x, w)
+        elif self.defect == "last_unwritten":
+            y = y[:-1]
+        mem.h2d(d_out, y)
+        if self.defect == "guard" and d_in != d_out:
+            mem.h2d(d_out - 4, np.zeros(1, np.uint32))  # the last word of the guard row before the output
+        if self.defect == "input_later_slice" and d_in != d_out:
+            mem.h2d(d_in + (2 * step + 5) * rb + 8, np.zeros(1, np.uint32))
+
+
+@pytest.fixture
+def small_slices(host_memory, monkeypatch):
+    monkeypatch.setattr(A, "SLICE_BYTES", 16 * STREAM_N * 300)  # 300 rows per slice: 1000 rows in four slices
+
+
+@pytest.mark.parametrize("dt", [np.complex64, np.complex128])
+def test_streamed_correct_plan_passes(small_slices, dt):
+    assert -(-STREAM_BATCH // A._slice_rows(16 * STREAM_N)) >= 3
+    for d in (-1, 1):
+        seen = []
+        e = A.check_execute_streamed(StreamedPlan(STREAM_N, STREAM_BATCH, d, dt), STREAM_N, STREAM_BATCH, dt, STREAM_SEED, "multipass",
+                                     label="numpy plan", expect=lambda: seen.append(1), long_rows=2 if dt == np.complex128 else 0)
+        assert 0 <= e <= A.bound("multipass", dt, STREAM_N) / 2
+        assert len(seen) == 2  # after the out-of-place and the in-place sync
+
+
+@pytest.mark.parametrize("defect,match", [
+    ("bin_last_slice", "1 of 100 transforms over the bound.*worst transform 998 \\(bin 77"),
+    ("swap_across_slices", "worst transform 29[9]"),
+    ("wrapped_index", "300 of 300 transforms over the bound"),  # rows 0 .. 511 hold transforms 512 .. 999
+    ("last_unwritten", "worst transform 999 .*non-finite 1"),
+    ("guard", "wrote outside"),
+    ("input_later_slice", "changed its input \\(transform 605\\)"),
+])
+def test_streamed_defects_flagged(small_slices, defect, match):
+    plan = StreamedPlan(STREAM_N, STREAM_BATCH, -1, np.complex64, defect=defect)
+    with pytest.raises(AssertionError, match=match):
+        A.check_execute_streamed(plan, STREAM_N, STREAM_BATCH, np.complex64, STREAM_SEED, "multipass", label="defect " + defect)
+
+
+def test_streamed_in_place_must_match_out_of_place(small_slices):
+    class InPlaceDiffers(StreamedPlan):
+        def execute_ptr(self, d_in, d_out):
+            super().execute_ptr(d_in, d_out)
+            if d_in == d_out:  # one last-bit change in the third slice: within the bound, but not the same bits
+                mem = A.memory()
+                w = mem.d2h(d_out + 700 * STREAM_N * 8, (1,), np.uint32)
+                mem.h2d(d_out + 700 * STREAM_N * 8, w ^ np.uint32(1))
+
+    with pytest.raises(AssertionError, match="in-place result differs from the out-of-place one at transform 700"):
+        A.check_execute_streamed(InPlaceDiffers(STREAM_N, STREAM_BATCH, -1, np.complex64), STREAM_N, STREAM_BATCH, np.complex64,
+                                 STREAM_SEED, "multipass")
+
+
+def test_streamed_exact_flags_any_changed_word(small_slices):
+    """exact=True (n = 1 plans): the output must be the input bit for bit."""
+    class Identity(NumpyPlan):
+        def execute_ptr(self, d_in, d_out):
+            mem = A.memory()
+            x = mem.d2h(d_in, (self.batch, 1), self.dtype)
+            x[640, 0] = np.nextafter(x[640, 0].real, np.float32(np.inf)) + 1j * x[640, 0].imag
+            mem.h2d(d_out, x)
+
+    A.check_execute_streamed(NumpyPlan(1, 5000, -1, np.complex64), 1, 5000, np.complex64, 3, "multipass", exact=True)
+    with pytest.raises(AssertionError, match="output differs from the input at transform 640"):
+        A.check_execute_streamed(Identity(1, 5000, -1, np.complex64), 1, 5000, np.complex64, 3, "multipass", exact=True)
+
+
+def test_block_rows_are_regenerable():
+    n, dt = 64, np.complex64
+    R = A.block_rows(n, dt)
+    a = A.block_normal_rows(n, 0, 3 * R + 5, dt, seed=9)
+    b = A.block_normal_rows(n, R - 2, R + 7, dt, seed=9)  # across a block boundary
+    assert np.array_equal(a[R - 2:2 * R + 5], b)
+    assert not np.array_equal(a[R - 1], a[R]) and not np.array_equal(a[0], a[1])
+    assert not np.array_equal(a[:R], A.block_normal_rows(n, 0, R, dt, seed=10))
+    c = A.block_normal_rows(4096, 0, 300, np.complex128, seed=2)
+    assert np.array_equal(c[123:201], A.block_normal_rows(4096, 123, 78, np.complex128, seed=2))
