@@ -42,6 +42,7 @@
 #include "fft_kernels_chain.h"
 #include "fft_team_list.h"
 #include "fft_team_defer.h"
+#include "fft_mixed_radix.h"
 #if defined(FFT_EMU)
 #include "fft_team_quad.h"
 #include "fft_wide_row.h"
@@ -86,7 +87,7 @@ struct ExecHooks {
     int mid_mode = fftk::HOOK_NONE;
 };
 
-enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6 };
+enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6, ALGO_MIXED_RADIX = 7 };
 
 struct PassDesc {
     int log2L = 0, log2C = 0, E = 16;
@@ -1733,6 +1734,280 @@ class BluesteinPlan {
         core.execute(work, work, nb, true);  // carries the 1/m
         rt->launch(fftk::mul_store_kernel<T>, (long long)bpr_n * nb, 256, (size_t)0, (const cpx<T>*)work, m, (const cpx<T>*)chirp, 0ll,
                    (int)fftk::HOOK_MUL_CONJ, out, (long long)n, n, scale, bpr_n);
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Mixed-radix plan (fft_mixed_radix.h): direct Stockham transforms of the 7-smooth lengths n = 2^a 3^b 5^c 7^d.
+//   n <= 4096            one pass, one HBM round trip
+//   n = n1 * n2 <= 2^23  two passes (four-step): columns of length n1 with the twiddle W_n^(k1 j2) into a scratch image
+//                        of the input's shape, then rows of length n2 stored transposed.  Every 7-smooth n <= 2^23 has a
+//                        split with both factors <= 4096 (the first that has none is 9 565 938).
+// The batch runs in launch groups as in Pow2Plan (FFT_HIP_CHUNK_MB), so that the scratch image stays cache resident.
+// ---------------------------------------------------------------------------
+constexpr int MR_MAX_L = 4096;
+constexpr long long MR_MAX_N = 1ll << 23;
+
+inline bool mr_is_smooth7(long long n) {
+    if (n < 1) return false;
+    for (int p : {2, 3, 5, 7})
+        while (n % p == 0) n /= p;
+    return n == 1;
+}
+
+// n = n1 * n2 with both factors in [2, max_l]: the split with the shortest longer factor, odd factors of an even n
+// (which cost fp32 its 16-byte accesses) counted as half as long again each; returns n1, 0 if there is none
+inline int mr_split(long long n, int max_l = MR_MAX_L) {
+    int best = 0;
+    long long best_cost = 0;
+    for (long long n1 = 2; n1 <= max_l && n1 * 2 <= n; n1++) {
+        if (n % n1) continue;
+        const long long n2 = n / n1;
+        if (n2 > max_l) continue;
+        const long long odd = (n & 1) ? 0 : (n1 & 1) + (n2 & 1);
+        const long long cost = std::max(n1, n2) * (2 + odd);
+        if (!best || cost < best_cost) { best = (int)n1; best_cost = cost; }
+    }
+    return best;
+}
+
+// 0: not a length of the mixed-radix plan, 1: single pass, 2: two passes (pure arithmetic, no device)
+inline int mr_passes(long long n) {
+    if (n < 1 || n > MR_MAX_N || !mr_is_smooth7(n)) return 0;
+    if (n <= MR_MAX_L) return 1;
+    return mr_split(n) ? 2 : 0;
+}
+
+template <typename T, typename RT>
+class MixedRadixPlan {
+  public:
+    static constexpr int V = 16 / (int)sizeof(cpx<T>);
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+#if defined(FFT_EMU)
+    static constexpr int kThreads = 32, kMaxNE = 256;  // host threads per workgroup: few, each carrying more
+#else
+    static constexpr int kThreads = 256, kMaxNE = (SZ == 8 ? 32 : 16);
+#endif
+
+    struct Pass {
+        fftk::MixedParams<T> p;
+        cpx<T>* tables = nullptr;
+        int smem = 0, ne = 0;
+    };
+
+    RT* rt = nullptr;
+    int n = 0, n1 = 0, n2 = 0, max_batch = 1, chunk = 1;
+    std::vector<Pass> passes;
+    cpx<T>* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    bool ok = false;
+
+    ~MixedRadixPlan() {
+        if (!rt) return;
+        for (auto& ps : passes) rt->dfree(ps.tables);
+        if (scratch) rt->dfree(scratch);
+    }
+
+    static unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
+
+    // stage schedule of a sub-transform of length L: radix 8 first (the first stage has no twiddles), then 4 or 2, then 7, 5, 3
+    static int schedule(int L, fftk::MrStage* st) {
+        int radices[32], nr = 0, a = 0, rest = L;
+        while (rest % 2 == 0) { rest /= 2; a++; }
+        while (a >= 3 && a != 4) { radices[nr++] = 8; a -= 3; }
+        while (a >= 2) { radices[nr++] = 4; a -= 2; }
+        if (a) radices[nr++] = 2;
+        for (int p : {7, 5, 3})
+            while (rest % p == 0) { radices[nr++] = p; rest /= p; }
+        if (rest != 1 || nr > fftk::MR_MAX_STAGES) return 0;
+        int Ns = 1;
+        for (int s = 0; s < nr; s++) {
+            fftk::MrStage& g = st[s];
+            g.radix = radices[s];
+            g.Ns = Ns;
+            g.m = L / g.radix;
+            g.tws = L / (Ns * g.radix);
+            g.mag_Ns = magic(Ns);
+            g.mag_m = magic(g.m);
+            Ns *= g.radix;
+        }
+        return nr;
+    }
+
+    static int lds_need(int L, int C, int tables_elems) {
+        const long long P = L | 1, D = (C * P + 1) & ~1ll;
+        const long long b = (2 * D + tables_elems) * SZ;
+        return b > 0x7fffffff ? 0x7fffffff : (int)b;
+    }
+
+    // One pass over sub-transforms of length L, n_sub of them per transform; ntw > 0: the W_ntw^(k c) inter-pass twiddle
+    // rides on the store.  Chooses C (sub-transforms per tile), builds the tables.
+    bool make_pass(Pass& ps, int L, int in_mode, int out_mode, int n_sub, long long ntw) {
+        fftk::MixedParams<T>& p = ps.p;
+        memset(&p, 0, sizeof(p));
+        p.nst = schedule(L, p.st);
+        if (!p.nst) return false;
+        p.L = L;
+        p.P = L | 1;
+        p.mag_L = magic(L);
+        p.in_mode = in_mode;
+        p.out_mode = out_mode;
+        p.n_sub = n_sub;
+        // tables: [ W_L ] [ W_ntw by bytes of the exponent ]
+        std::vector<cpx<T>> blob, part;
+        p.tw_two = L > 1024 ? 1 : 0;
+        if (p.tw_two) {
+            make_twiddle_table<T>(blob, L, 64, 1);
+            p.o_hi = 64;
+            make_twiddle_table<T>(part, L, ((L - 1) >> 6) + 1, 64);
+            blob.insert(blob.end(), part.begin(), part.end());
+        } else {
+            make_twiddle_table<T>(blob, L, L, 1);
+        }
+        if (ntw > 0) {
+            p.ptw_levels = ntw > 65536 ? 3 : 2;
+            p.o_p0 = (int)blob.size();
+            make_twiddle_table<T>(part, ntw, 256, 1);
+            blob.insert(blob.end(), part.begin(), part.end());
+            p.o_p1 = (int)blob.size();
+            make_twiddle_table<T>(part, ntw, 256, 256);
+            blob.insert(blob.end(), part.begin(), part.end());
+            p.o_p2 = (int)blob.size();
+            if (p.ptw_levels > 2) {
+                make_twiddle_table<T>(part, ntw, ((ntw - 1) >> 16) + 1, 65536);
+                blob.insert(blob.end(), part.begin(), part.end());
+            }
+        }
+        if (blob.size() & 1) blob.push_back(blob[0]);
+        p.tables_elems = (int)blob.size();
+        // tile: tens of KiB of data, at most what the threads carry in registers
+        const bool cols = in_mode == fftk::MR_COLS || out_mode == fftk::MR_COLS;
+        const int cap = kMaxNE * kThreads, target = SZ == 8 ? 4096 : 2048;
+        const int budget = rt->max_lds_bytes();
+        int C;
+        if (cols) {
+            C = V;
+            while (C * 2 <= 64 && C * 2 * L <= target && C < n_sub) C *= 2;
+            if (C * L > cap) return false;
+            while (lds_need(L, C, p.tables_elems) > budget && C > V) C /= 2;
+        } else {
+            C = std::max(1, std::min(target / L, n_sub));
+            if (V == 2 && ((C * L) & 1) && C < n_sub && (C + 1) * L <= cap) C++;
+            if (C * L > cap) return false;
+            while (lds_need(L, C, p.tables_elems) > budget && C > 1) C /= 2;
+        }
+        if (lds_need(L, C, p.tables_elems) > budget) return false;
+        p.C = C;
+        p.log2C = ilog2(C);
+        p.tpt = (n_sub + C - 1) / C;
+        ps.smem = lds_need(L, C, p.tables_elems);
+        const int need = (C * L + kThreads - 1) / kThreads;
+#if defined(FFT_EMU)
+        ps.ne = kMaxNE;
+        (void)need;
+#else
+        ps.ne = need <= 8 ? 8 : need <= 16 ? 16 : 32;
+#endif
+        ps.tables = (cpx<T>*)rt->dmalloc(blob.size() * SZ);
+        if (!ps.tables) return false;
+        rt->h2d(ps.tables, blob.data(), blob.size() * SZ);
+        p.tables = ps.tables;
+        return true;
+    }
+
+    // the longest sub-transform whose smallest tile fits the LDS budget
+    int max_len() const {
+        int l = MR_MAX_L;
+        while (l > 2 && lds_need(l, V, (l > 1024 ? 64 + ((l - 1) >> 6) + 1 : l) + 640) > rt->max_lds_bytes()) l--;
+        return l;
+    }
+
+    bool build(RT* runtime, int n_, int batch) {
+        rt = runtime;
+        n = n_;
+        max_batch = batch;
+        chunk = batch;
+        if (n < 2 || n > MR_MAX_N || !mr_is_smooth7(n)) return false;
+        const int lmax = max_len();
+        if (n <= lmax) {
+            passes.resize(1);
+            if (!make_pass(passes[0], n, fftk::MR_ROWS, fftk::MR_ROWS, batch, 0)) return false;
+            n1 = n;
+            n2 = 1;
+            ok = true;
+            return true;
+        }
+        n1 = mr_split(n, lmax);
+        if (!n1) return false;
+        n2 = n / n1;
+        passes.resize(2);
+        if (!make_pass(passes[0], n1, fftk::MR_COLS, fftk::MR_COLS, n2, n)) return false;
+        if (!make_pass(passes[1], n2, fftk::MR_ROWS, fftk::MR_COLS, n1, 0)) return false;
+        passes[0].p.in_stride = passes[0].p.out_stride = n2;
+        passes[1].p.out_stride = n1;
+        long long target = 1024ll << 20;  // scratch bytes per launch group, as in Pow2Plan
+        if (rt->policy.chunk_mb > 0) target = rt->policy.chunk_mb << 20;
+        const long long per = (long long)n * SZ;
+        chunk = (int)std::max(1ll, std::min<long long>(batch, target / per));
+        scratch_bytes = (size_t)chunk * (size_t)per;
+        scratch = (cpx<T>*)rt->dmalloc(scratch_bytes);
+        if (!scratch) return false;
+        ok = true;
+        return true;
+    }
+
+    template <int NE>
+    void launch_ne(const Pass& ps, const fftk::MixedParams<T>& p) {
+        const int occ = rt->max_blocks_per_cu(fftk::mixed_tile_kernel<T, NE>, kThreads, (size_t)ps.smem);
+        const long long grid = std::min<long long>(p.ntiles, (long long)rt->num_cus() * occ);
+        rt->launch(fftk::mixed_tile_kernel<T, NE>, grid, kThreads, (size_t)ps.smem, p);
+    }
+
+    // a side's accesses are all 16-byte aligned (fp32; fp64 values are 16 bytes)
+    static bool vec_ok(const fftk::MixedParams<T>& p, int mode, const void* ptr, long long stride, int n_tr) {
+        if (V != 2 || ((uintptr_t)ptr & 15)) return false;
+        if (n_tr > 1 && (p.tr_stride & 1)) return false;
+        if (mode == fftk::MR_ROWS) return p.tpt == 1 || !((p.C * p.L) & 1);
+        return !(stride & 1) && !(p.C & 1);
+    }
+
+    void launch_pass(Pass& ps, const cpx<T>* in, cpx<T>* out, int n_tr, int n_sub, bool swap_in, bool swap_out, T scale) {
+        fftk::MixedParams<T> p = ps.p;
+        p.in = in;
+        p.out = out;
+        p.n_sub = n_sub;
+        p.tpt = (n_sub + p.C - 1) / p.C;
+        p.ntiles = (long long)n_tr * p.tpt;
+        p.tr_stride = n;
+        p.in_vec = vec_ok(p, p.in_mode, in, p.in_stride, n_tr) ? 1 : 0;
+        p.out_vec = vec_ok(p, p.out_mode, out, p.out_stride, n_tr) ? 1 : 0;
+        p.swap_in = swap_in ? 1 : 0;
+        p.swap_out = swap_out ? 1 : 0;
+        p.scale = scale;
+        if (p.ntiles <= 0) return;
+#if defined(FFT_EMU)
+        launch_ne<kMaxNE>(ps, p);
+#else
+        if (ps.ne == 8) launch_ne<8>(ps, p);
+        else if (ps.ne == 16) launch_ne<16>(ps, p);
+        else if constexpr (SZ == 8) launch_ne<32>(ps, p);
+#endif
+    }
+
+    void execute(const cpx<T>* in, cpx<T>* out, int nb, bool inverse) {
+        const T scale = inverse ? (T)(1.0L / (long double)n) : (T)1;
+        if (passes.size() == 1) {  // the batch is one "transform" of nb rows
+            launch_pass(passes[0], in, out, 1, nb, inverse, inverse, scale);
+            rt->mark(0);
+            return;
+        }
+        for (int b0 = 0; b0 < nb; b0 += chunk) {
+            const int cb = (nb - b0) < chunk ? (nb - b0) : chunk;
+            launch_pass(passes[0], in + (size_t)b0 * (size_t)n, scratch, cb, n2, inverse, false, (T)1);
+            rt->mark(0);
+            launch_pass(passes[1], scratch, out + (size_t)b0 * (size_t)n, cb, n1, false, inverse, scale);
+            rt->mark(1);
+        }
     }
 };
 

@@ -229,6 +229,7 @@ int g_initialized = 0;
 int g_device = 0;
 char g_device_name[256] = "No GPU";
 ffteng::EnginePolicy g_policy;  // read from the environment once, at fft_gpu_init_hip
+int g_smooth_policy = 0;        // fft_gpu_set_smooth_policy_hip: 1 = AUTO builds the mixed-radix plan for 7-smooth lengths
 
 // Per-device facts the planner needs, read from THAT device's properties the first time a plan or buffer is made on it
 // (an 8-GPU process sets each device in turn; nothing is cached from the first device for the others).
@@ -299,6 +300,8 @@ struct fft_gpu_plan {
     ffteng::Pow2Plan<double, HipRT>* p64 = nullptr;
     ffteng::BluesteinPlan<float, HipRT>* b32 = nullptr;
     ffteng::BluesteinPlan<double, HipRT>* b64 = nullptr;
+    ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
+    ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
     int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer
     int rows = 0, cols = 0;
@@ -447,6 +450,8 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
         else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb, inv);
         else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, nb);
         else if (p->b64) p->b64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb);
+        else if (p->m32) p->m32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, nb, inv);
+        else if (p->m64) p->m64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb, inv);
         else return -1;
         hipError_t e2 = hipGetLastError();
         if (e2 != hipSuccess) {
@@ -466,6 +471,8 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
     else if (p->b64) p->b64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch);
+    else if (p->m32) p->m32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
+    else if (p->m64) p->m64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else return -1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -513,6 +520,7 @@ int fft_gpu_init_hip(void) {
     if (const char* e = getenv("FFT_HIP_TEAM")) g_policy.team_mode = atoi(e);
     if (const char* e = getenv("FFT_HIP_TEAM_MIN_BATCH")) g_policy.team_min_batch = atoi(e);
     if (const char* e = getenv("FFT_HIP_CHUNK_MB")) g_policy.chunk_mb = atoll(e);
+    if (const char* e = getenv("FFT_HIP_SMOOTH")) g_smooth_policy = atoi(e) == 1 ? 1 : 0;
     g_initialized = 1;
     pthread_mutex_unlock(&g_lock);
     return 0;
@@ -616,7 +624,7 @@ fft_gpu_plan_t fft_gpu_plan_1d_ex_hip(int n, int batch, fft_direction dir, fft_p
         fprintf(stderr, "fft_hip: plan requested before fft_gpu_init\n");
         return NULL;
     }
-    if (n <= 0 || batch <= 0 || (prec != FFT_PREC_F32 && prec != FFT_PREC_F64) || (int)algo < 0 || (int)algo > 6) {
+    if (n <= 0 || batch <= 0 || (prec != FFT_PREC_F32 && prec != FFT_PREC_F64) || (int)algo < 0 || (int)algo > 7) {
         fprintf(stderr, "fft_hip: invalid plan arguments (n=%d batch=%d prec=%d algo=%d)\n", n, batch, (int)prec, (int)algo);
         return NULL;
     }
@@ -629,6 +637,11 @@ fft_gpu_plan_t fft_gpu_plan_1d_ex_hip(int n, int batch, fft_direction dir, fft_p
     p->algo = (int)algo;
     p->pow2 = (n & (n - 1)) == 0 && algo != FFT_GPU_ALGO_BLUESTEIN;
     if (algo == FFT_GPU_ALGO_BLUESTEIN) algo = FFT_GPU_ALGO_AUTO;
+    // 7-smooth lengths: the mixed-radix plan when asked for by name, or by AUTO under the smooth policy; a power of two keeps
+    // the plan AUTO builds, any other length falls back to chirp-z
+    bool mixed = !p->pow2 && (algo == FFT_GPU_ALGO_MIXED_RADIX || (algo == FFT_GPU_ALGO_AUTO && p->algo == FFT_GPU_ALGO_AUTO && g_smooth_policy == 1)) &&
+                 ffteng::mr_passes(n) > 0;
+    if (algo == FFT_GPU_ALGO_MIXED_RADIX) algo = FFT_GPU_ALGO_AUTO;
     int dev = g_device;
     (void)hipGetDevice(&dev);
     p->device = dev;
@@ -658,7 +671,20 @@ fft_gpu_plan_t fft_gpu_plan_1d_ex_hip(int n, int batch, fft_direction dir, fft_p
             p->p64 = new (std::nothrow) ffteng::Pow2Plan<double, HipRT>();
             ok = p->p64 && p->p64->build(&p->rt, log2n, (int)algo, batch);
         }
-    } else {
+    }
+    if (!p->pow2 && mixed) {
+        if (prec == FFT_PREC_F32) {
+            p->m32 = new (std::nothrow) ffteng::MixedRadixPlan<float, HipRT>();
+            ok = p->m32 && p->m32->build(&p->rt, n, batch);
+            if (!ok) { delete p->m32; p->m32 = nullptr; }
+        } else {
+            p->m64 = new (std::nothrow) ffteng::MixedRadixPlan<double, HipRT>();
+            ok = p->m64 && p->m64->build(&p->rt, n, batch);
+            if (!ok) { delete p->m64; p->m64 = nullptr; }
+        }
+        mixed = ok;  // (a device whose LDS holds no such schedule: chirp-z)
+    }
+    if (!p->pow2 && !mixed) {
         if (n > (1 << 29)) {
             fprintf(stderr, "fft_hip: Bluestein length %d too large\n", n);
         } else if (prec == FFT_PREC_F32) {
@@ -693,6 +719,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->p64;
         delete p->b32;
         delete p->b64;
+        delete p->m32;
+        delete p->m64;
         delete p->d32;
         delete p->d64;
         delete p->r32;
@@ -875,6 +903,18 @@ int fft_gpu_set_policy_hip(int team_mode, int team_min_batch, int chunk_mb) {
     pthread_mutex_unlock(&g_lock);
     return 0;
 }
+
+// 0 (default): AUTO keeps chirp-z for every non-power-of-two length; 1: AUTO builds the mixed-radix plan wherever
+// fft_gpu_mixed_radix_passes_hip(n) > 0.  Plans created after the call; a negative argument changes nothing.  Returns the mode in force.
+int fft_gpu_set_smooth_policy_hip(int mode) {
+    pthread_mutex_lock(&g_lock);
+    if (mode >= 0) g_smooth_policy = mode == 1 ? 1 : 0;
+    const int now = g_smooth_policy;
+    pthread_mutex_unlock(&g_lock);
+    return now;
+}
+
+int fft_gpu_mixed_radix_passes_hip(int n) { return ffteng::mr_passes(n); }
 
 int fft_gpu_host_register_hip(void* host_ptr, size_t bytes) {
     if (!host_ptr || !bytes || !g_initialized) return -1;
@@ -1181,6 +1221,16 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         info->fused = (p->b64->core.hook_capable() && !p->b64->no_fusion) ? ((!p->b64->no_chain && p->b64->core.round_capable()) ? 3 : (!p->b64->no_chain && p->b64->core.chain_capable()) ? 2 : 1) : 0;
         info->workspace_bytes += (size_t)p->batch * ((size_t)1 << p->b64->log2m) * sizeof(complex_t);
     }
+    auto fill_mixed = [&](auto* m) {
+        info->algo = ffteng::ALGO_MIXED_RADIX;
+        info->n_passes = (int)m->passes.size();
+        info->factors[0] = m->n1;
+        if (m->passes.size() > 1) info->factors[1] = m->n2;
+        info->chunk_batch = m->chunk;
+        info->workspace_bytes += m->scratch_bytes;
+    };
+    if (p->m32) fill_mixed(p->m32);
+    if (p->m64) fill_mixed(p->m64);
     auto fill_fused = [&](auto* f) {  // fused consumers: the padded transform behind them
         fill(&f->core);
         const bool pair = !f->no_chain && f->kind != ffteng::FUSED_PSD;

@@ -18,8 +18,8 @@ FFT_GPU_AUTO = -1
 FFT_GPU_HIP = 4
 PREC_F64 = 0
 PREC_F32 = 1
-ALGO_AUTO, ALGO_RADIX2, ALGO_RADIX4, ALGO_SPLIT_RADIX, ALGO_RADIX2_GLOBAL, ALGO_BLUESTEIN, ALGO_RADIX2_SHFL = range(7)
-ALGO_NAMES = {"auto": 0, "radix2": 1, "radix4": 2, "split_radix": 3, "radix2_global": 4, "bluestein": 5, "radix2_shfl": 6}
+ALGO_AUTO, ALGO_RADIX2, ALGO_RADIX4, ALGO_SPLIT_RADIX, ALGO_RADIX2_GLOBAL, ALGO_BLUESTEIN, ALGO_RADIX2_SHFL, ALGO_MIXED_RADIX = range(8)
+ALGO_NAMES = {"auto": 0, "radix2": 1, "radix4": 2, "split_radix": 3, "radix2_global": 4, "bluestein": 5, "radix2_shfl": 6, "mixed_radix": 7}
 FFT_PREFER_GPU = 1 << 9
 HIP_STREAM_LEGACY = 1  # hipStreamLegacy: the NULL / default stream named explicitly (fft_gpu_plan_set_stream: NULL = the plan's own)
 
@@ -59,6 +59,7 @@ SIGNATURES = {
     "fft_gpu_plan_info_hip": (_i, [_vp, C.POINTER(PlanInfo)]), "fft_gpu_plan_set_stream_hip": (_i, [_vp, _vp]),
     "fft_gpu_execute_ptr_hip": (_i, [_vp, _vp, _vp]), "fft_gpu_plan_sync_hip": (_i, [_vp]),
     "fft_gpu_plan_set_option_hip": (_i, [_vp, _i, _i]), "fft_gpu_set_policy_hip": (_i, [_i, _i, _i]),
+    "fft_gpu_mixed_radix_passes_hip": (_i, [_i]), "fft_gpu_set_smooth_policy_hip": (_i, [_i]),
     "fft_gpu_plan_2d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_2d_ex_hip": (_vp, [_i, _i, _i, _i, _i]),
     "fft_gpu_plan_r2c_1d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_c2r_1d_hip": (_vp, [_i, _i, _i]),
     "fft_gpu_plan_fused_hip": (_vp, [_i, _i, _i, _vp, _i, _i]), "fft_gpu_fused_out_len_hip": (_i, [_vp]),
@@ -99,7 +100,7 @@ SIGNATURES = {
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
     "radix4_fft_gpu": (_i, [_vp, _i, _i]), "split_radix_fft_gpu": (_i, [_vp, _i, _i]),
-    "bluestein_fft_gpu": (_i, [_vp, _i, _i]),
+    "bluestein_fft_gpu": (_i, [_vp, _i, _i]), "fft_mixed_radix_gpu": (_i, [_vp, _i, _i]),
 }
 
 _lib = None
@@ -148,6 +149,16 @@ def set_device(index):
 def get_device():
     """The device new plans and buffers currently live on (fft_gpu_get_device_hip)."""
     return load().fft_gpu_get_device_hip()
+
+
+def set_smooth_policy(mode=-1):
+    """Which plan ALGO_AUTO builds for 7-smooth lengths from now on: 0 chirp-z (default), 1 mixed radix; -1 only asks.  Returns the mode in force."""
+    return load().fft_gpu_set_smooth_policy_hip(mode)
+
+
+def mixed_radix_passes(n):
+    """0: n is not a mixed-radix length; 1 / 2: passes of the mixed-radix plan (no device needed)."""
+    return load().fft_gpu_mixed_radix_passes_hip(n)
 
 
 def set_policy(team=-1, min_batch=-1, chunk_mb=-1):

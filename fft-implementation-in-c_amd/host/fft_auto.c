@@ -66,12 +66,17 @@ static int ensure_gpu(void) {
 /* FFT_MEASURE (reference TODO fft_auto.c:232-235): time the candidate schedules for a single transform of length n on the
  * device -- AUTO's pick and the explicit radix-4 / radix-2 families for a power of two -- and keep the fastest plan. */
 static fft_gpu_plan_t measured_plan(int n, fft_direction dir, fft_gpu_memory_t buf, int* winner) {
-    static const fft_gpu_algo_t candidates[3] = {FFT_GPU_ALGO_AUTO, FFT_GPU_ALGO_RADIX4, FFT_GPU_ALGO_RADIX2};
-    const int n_cand = is_power_of_two(n) && n >= 4 ? 3 : 1;
+    static const fft_gpu_algo_t pow2_candidates[3] = {FFT_GPU_ALGO_AUTO, FFT_GPU_ALGO_RADIX4, FFT_GPU_ALGO_RADIX2};
+    /* a 7-smooth length under the smooth policy: chirp-z (AUTO planned as before the policy) against the mixed-radix plan */
+    static const fft_gpu_algo_t smooth_candidates[2] = {FFT_GPU_ALGO_AUTO, FFT_GPU_ALGO_MIXED_RADIX};
+    const int smooth = !is_power_of_two(n) && fft_gpu_set_smooth_policy_hip(-1) == 1 && fft_gpu_mixed_radix_passes_hip(n) > 0;
+    const fft_gpu_algo_t* candidates = smooth ? smooth_candidates : pow2_candidates;
+    const int n_cand = smooth ? 2 : (is_power_of_two(n) && n >= 4 ? 3 : 1);
     fft_gpu_plan_t best = NULL;
     float best_ms = 0.f;
     for (int c = 0; c < n_cand; c++) {
-        fft_gpu_plan_t p = fft_gpu_plan_1d_ex(n, 1, dir, FFT_PREC_F64, candidates[c]);
+        /* (chirp-z by name: under the smooth policy AUTO itself would build the mixed-radix plan; the same plan as AUTO under policy 0) */
+        fft_gpu_plan_t p = fft_gpu_plan_1d_ex(n, 1, dir, FFT_PREC_F64, (smooth && c == 0) ? FFT_GPU_ALGO_BLUESTEIN : candidates[c]);
         if (!p) continue;
         float ms = 0.f;
         void* d = fft_gpu_memory_ptr(buf);
@@ -362,6 +367,10 @@ int radix2_dit_fft_gpu(complex_t* x, int n, fft_direction dir) { return run_algo
 int radix2_fft_gpu(complex_t* x, int n, fft_direction dir) { return run_algo(x, n, dir, FFT_GPU_ALGO_RADIX2, 1); }
 int radix4_fft_gpu(complex_t* x, int n, fft_direction dir) { return run_algo(x, n, dir, FFT_GPU_ALGO_RADIX4, 1); }
 int split_radix_fft_gpu(complex_t* x, int n, fft_direction dir) { return run_algo(x, n, dir, FFT_GPU_ALGO_SPLIT_RADIX, 1); }
+int fft_mixed_radix_gpu(complex_t* x, int n, fft_direction dir) {
+    /* 7-smooth n: direct Stockham mixed-radix; a power of two: AUTO's plan; any other n: chirp-z.  The inverse is scaled by 1/n */
+    return run_algo(x, n, dir, FFT_GPU_ALGO_MIXED_RADIX, 0);
+}
 int bluestein_fft_gpu(complex_t* x, int n, fft_direction dir) {
     /* any n: a power of two is padded like any other length (m = next_pow2(2n-1), bluestein.c:87) */
     return run_algo(x, n, dir, FFT_GPU_ALGO_BLUESTEIN, 0);

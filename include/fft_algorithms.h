@@ -22,6 +22,8 @@ int radix2_fft_gpu(complex_t* x, int n, fft_direction dir);      /* LDS Stockham
 int radix4_fft_gpu(complex_t* x, int n, fft_direction dir);      /* LDS Stockham radix-4 */
 int split_radix_fft_gpu(complex_t* x, int n, fft_direction dir); /* LDS Stockham, split-radix codelets */
 int bluestein_fft_gpu(complex_t* x, int n, fft_direction dir);   /* chirp-z over the power-of-two engine, any n */
+int fft_mixed_radix_gpu(complex_t* x, int n, fft_direction dir); /* Stockham mixed-radix for n = 2^a 3^b 5^c 7^d <= 2^23 (other n: as AUTO);
+                                                                    the inverse is scaled by 1/n */
 
 #ifdef __cplusplus
 }

@@ -63,11 +63,15 @@ typedef enum {
     FFT_GPU_ALGO_SPLIT_RADIX = 3,   /* LDS Stockham, radix-8/16 passes with split-radix (L-shaped) codelets */
     FFT_GPU_ALGO_RADIX2_GLOBAL = 4, /* reference-shaped: bit-reversal permutation kernel + log2(n)
                                        in-place radix-2 DIT stage kernels in HBM (radix2_dit.c:70-112) */
-    FFT_GPU_ALGO_BLUESTEIN = 5,     /* chirp-z even when n is a power of two (bluestein.c:79-155);
-                                       every non-power-of-two n uses it whatever algo says */
-    FFT_GPU_ALGO_RADIX2_SHFL = 6    /* reference-shaped radix-2 DIT held by one wavefront per transform: LDS
+    FFT_GPU_ALGO_BLUESTEIN = 5,     /* chirp-z even when n is a power of two (bluestein.c:79-155); every non-power-of-two
+                                       n uses it whatever algo says, except a 7-smooth n planned with
+                                       FFT_GPU_ALGO_MIXED_RADIX (or with AUTO under fft_gpu_set_smooth_policy_hip(1)) */
+    FFT_GPU_ALGO_RADIX2_SHFL = 6,   /* reference-shaped radix-2 DIT held by one wavefront per transform: LDS
                                        bit-reversal permutation, in-register stages, __shfl_xor for the
                                        cross-lane strides (n = 128..1024; other n: FFT_GPU_ALGO_RADIX2) */
+    FFT_GPU_ALGO_MIXED_RADIX = 7    /* direct Stockham mixed-radix (radix 2, 3, 4, 5, 7, 8 through LDS) for the 7-smooth
+                                       n = 2^a 3^b 5^c 7^d <= 2^23: one pass up to 4096, two above; a power of two gets
+                                       the plan AUTO builds, any other n chirp-z */
 } fft_gpu_algo_t;
 
 typedef struct {
@@ -183,6 +187,13 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t plan, fft_gpu_plan_option_t optio
  * team_min_batch: 0 = the measured batch crossover; chunk_mb: 0 = the default multi-pass launch-group size.
  * fft_gpu_init seeds them once from FFT_HIP_TEAM / FFT_HIP_TEAM_MIN_BATCH / FFT_HIP_CHUNK_MB. */
 int fft_gpu_set_policy_hip(int team_mode, int team_min_batch, int chunk_mb);
+/* what FFT_GPU_ALGO_MIXED_RADIX does with n: 0 not a mixed-radix length (not 7-smooth, above 2^23, n <= 0), 1 a single pass,
+ * 2 two passes.  Host arithmetic only: works without a device. */
+int fft_gpu_mixed_radix_passes_hip(int n);
+/* which plan FFT_GPU_ALGO_AUTO builds for a non-power-of-two n, for plans created after the call: 0 (default) chirp-z, 1 the
+ * mixed-radix plan wherever fft_gpu_mixed_radix_passes_hip(n) > 0.  A negative argument changes nothing; returns the mode in
+ * force.  fft_gpu_init seeds it once from FFT_HIP_SMOOTH. */
+int fft_gpu_set_smooth_policy_hip(int mode);
 /* syncs the plan's stream, then: 0 the last execute was done by the team kernel, 1 its XCD teams could not be
  * formed and the multi-pass fallback did the work, 2 a team barrier timed out (results invalid; plan_sync returns -1
  * too), -1 the plan has no team kernel or it has never been launched */
