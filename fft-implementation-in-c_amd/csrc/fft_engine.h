@@ -18,6 +18,15 @@
 //   long long team_form_timeout_ticks();   // bound of team formation (shared device -> multi-pass fallback)
 //   EnginePolicy policy;                   // the few production knobs, read once when the runtime is set up
 //   template <class K, class... A> void launch_coresident(K kernel, long long grid, int block, size_t smem, A... args);
+//   void  d2d_async(void* dst, const void* src, size_t bytes);
+//   Which kernel of a family runs.  The built shapes of a family are ONE list next to its declaration (fft_team_quad_decl.h,
+//   fft_wide_row.h, fft_team_list.h); the planner plans those and nothing else, so the hooks below are switches, not size tables:
+//   bool  team_default_on(int elem_bytes, int log2n);   // policy.team_mode == 1: the sizes where a team kernel measured faster
+//   bool  team_quad(int elem_bytes, int log2n);          // team_quad_kernel instead of the tile-by-tile team kernels: on / off / per size
+//   int   team_quad_slots(int elem_bytes, int log2n, int log2TS);  // optional: its exchange protocol to ask for (1, 2, 3; not built, or no hook:
+//                                                        // the first one listed for the shape)
+//   bool  wide_rows(int elem_bytes, int log2n);          // wide_row_kernel for the single-pass sizes it is built for: on / off
+//   bool  team_defer / team_asplit / team_pair / team_nodefer / team_alll2(int elem_bytes, int log2n);  // variants of the tile-by-tile team kernels
 //
 // Scheme (reference optimizations/parallel_fft.c:213-272 is the
 // CPU statement of the same four-step idea):
@@ -36,6 +45,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "fft_kernels.h"
@@ -48,13 +58,8 @@
 #include "fft_wide_row.h"
 #else
 #include "fft_team_quad_decl.h"
-#define FFT_WIDE_DECL_ONLY
+#define FFT_WIDE_DECL_ONLY  // the bodies are compiled in fft_team_quad.hip
 #include "fft_wide_row.h"
-namespace fftk {
-extern template __global__ void wide_row_kernel<float, 13>(WideParams<float>);
-extern template __global__ void wide_row_kernel<float, 14>(WideParams<float>);
-extern template __global__ void wide_row_kernel<double, 13, 16>(WideParams<double>);
-}
 #endif
 
 namespace ffteng {
@@ -134,6 +139,19 @@ inline int ilog2(long long v) {
     return l;
 }
 
+// a runtime value as a template argument: calls f(std::integral_constant<int, v>()) if LO <= v <= HI; false: out of range, nothing called
+template <int LO, int HI, class F>
+inline bool with_constant(int v, F&& f) {
+    if constexpr (LO <= HI) {
+        if (v == LO) {
+            f(std::integral_constant<int, LO>());
+            return true;
+        }
+        return with_constant<LO + 1, HI>(v, f);
+    }
+    return false;
+}
+
 template <typename T>
 static void make_twiddle_table(std::vector<cpx<T>>& t, long long period, long long count, long long step) {
     // t[i] = exp(-2 pi i * (i*step) / period), evaluated in long double, rounded once
@@ -164,6 +182,7 @@ struct TeamDesc {
     bool nodefer = false; // team_defer_kernel NODEFER (with PAIR): no deferred phase, two live windows per team
     bool pair = false;    // team_defer_kernel PAIR: adjacent row tiles in phases (0,1) / (2,3), 2 CB-row result segments (fp32)
     bool quad = false;    // team_quad_kernel (fft_team_quad.h): whole-line segments, both steps decimated by 4, exchange in four rounds
+    int quad_slots = 0;   // ... and its exchange protocol (the SLOTS of fft_team_quad_decl.h's list)
     int E = 0;  // elements per thread = stage radix (fp32: 16 -> 512 threads, 8 -> 1024 threads; fp64: 8)
     int data_bytes = 0, tables_elems = 0, smem_bytes = 0;
     int o_sb1 = 0, o_sa2 = 0, o_sb2 = 0, o_t0 = 0, o_t1 = 0, sa1_bits = 0, sa2_bits = 0, t0_bits = 0;
@@ -242,20 +261,18 @@ class Pow2Plan {
         scratch = nullptr;
     }
 
-    // ---- team_quad_kernel (fft_team_quad.h): n = L x L with L = 4 E^2, teams of TS = n / (4 tiles) seats.  Built for fp32
-    // n = 2^20 on the device (E = 16, a whole XCD per transform) and for n = 2^12 in the emulation (E = 4, 64-thread
-    // workgroups, teams of 4).  Tables [W_n^x, x < L | W_L^y, y < L]; window: 2 slots of TS images per team.
-    // ---- wide_row_kernel (fft_wide_row.h): single-pass n = 8192 fp32 (the emulation: n = 512, 32 threads)
+    // ---- wide_row_kernel (fft_wide_row.h, with the list of built sizes): single-pass n = 8192 fp32 (the emulation: n = 512, 32 threads)
     struct WideDesc {
         bool ok = false;
         int nthreads = 0, smem_bytes = 0, tables_elems = 0, o_sb = 0, sa_bits = 0;
         cpx<T>* tables = nullptr;
     } wide;
     void build_wide() {
-        if (!rt->wide_rows(SZ, log2n)) return;
+        const int E = fftk::wide_row_E<T>(log2n);
+        if (!E || !rt->wide_rows(SZ, log2n)) return;
         const long long L = 1ll << log2n;
         WideDesc d;
-        d.nthreads = (int)(L / 16);
+        d.nthreads = (int)(L / E);
         d.sa_bits = fftk::team_stage_table_bits(SZ, log2n);
         d.o_sb = 1 << d.sa_bits;
         int ne = d.o_sb + (1 << (log2n - d.sa_bits));
@@ -276,28 +293,18 @@ class Pow2Plan {
         wide = d;
     }
     void launch_wide(const cpx<T>* in, cpx<T>* out, int nb, bool inverse, T scale) {
-        if constexpr (SZ == 16) {
-#if !defined(FFT_EMU)
-            fftk::WideParams<T> wp;
-            memset(&wp, 0, sizeof(wp));
-            wp.in = in; wp.out = out; wp.tables = wide.tables; wp.tables_bytes = wide.tables_elems * SZ;
-            wp.o_sb = wide.o_sb; wp.sa_bits = wide.sa_bits; wp.nb = nb; wp.inverse = inverse ? 1 : 0; wp.nt = 3; wp.scale = scale;
-            rt->launch(fftk::wide_row_kernel<T, 13, 16>, std::min<long long>(nb, rt->num_cus()), wide.nthreads, (size_t)wide.smem_bytes, wp);
-#endif
-        }
-        if constexpr (SZ == 8) {
-            fftk::WideParams<T> wp;
-            memset(&wp, 0, sizeof(wp));
-            wp.in = in; wp.out = out; wp.tables = wide.tables; wp.tables_bytes = wide.tables_elems * SZ;
-            wp.o_sb = wide.o_sb; wp.sa_bits = wide.sa_bits; wp.nb = nb; wp.inverse = inverse ? 1 : 0; wp.nt = 3; wp.scale = scale;
-            const long long grid = std::min<long long>(nb, rt->num_cus());
-#if defined(FFT_EMU)
-            rt->launch(fftk::wide_row_kernel<T, 9>, grid, wide.nthreads, (size_t)wide.smem_bytes, wp);
-#else
-            if (log2n == 14) rt->launch(fftk::wide_row_kernel<T, 14>, grid, wide.nthreads, (size_t)wide.smem_bytes, wp);
-            else rt->launch(fftk::wide_row_kernel<T, 13>, grid, wide.nthreads, (size_t)wide.smem_bytes, wp);
-#endif
-        }
+        fftk::WideParams<T> wp;
+        memset(&wp, 0, sizeof(wp));
+        wp.in = in; wp.out = out; wp.tables = wide.tables; wp.tables_bytes = wide.tables_elems * SZ;
+        wp.o_sb = wide.o_sb; wp.sa_bits = wide.sa_bits; wp.nb = nb; wp.inverse = inverse ? 1 : 0; wp.nt = 3; wp.scale = scale;
+        const long long grid = std::min<long long>(nb, rt->num_cus());
+#define FFT_WIDE_GO(TT, LOG2L, E)                                                                                             \
+    if constexpr (std::is_same<T, TT>::value) {                                                                               \
+        if (log2n == (LOG2L)) return rt->launch(fftk::wide_row_kernel<TT, LOG2L, E>, grid, wide.nthreads, (size_t)wide.smem_bytes, wp); \
+    }
+        FFT_WIDE_INSTANCES(FFT_WIDE_GO)
+#undef FFT_WIDE_GO
+        (void)grid;
     }
 
     // ---- team_quad_kernel (fft_team_quad.h): n = L1 x L2 (L1 >= L2), L1 = 4 E RA, L2 = 4 E RB (E values per thread and chunk, a
@@ -305,15 +312,19 @@ class Pow2Plan {
     // teams of 32), 2^19 (16 8, 16), 2^18 (8 8, 8), 2^17 (8 4, 4), 2^16 (4 4, 2); emulation (E = 4): n = 2^12 (4 4), 2^11 (4 2)
     // and 2^10 (2 2).  Tables [W_n^x, x < L2/2 | W_L1^y, y < L1 | W_L2^y, y < L2 | W_n^(L2/2)]; window: 2 slots of TS images per team.
     // fp64 (one value per 16-byte access, 8 values per thread and chunk): n = 2^14 = 256 x 64 on one CU, 2^15 = 256 x 128 on teams of 2,
-    // 2^16 = 256 x 256 on teams of 4 (RA <= E: no larger size has two-stage sub-transforms).
-    static constexpr int quad_E(int log2n_) {
-        return SZ == 8 ? ((log2n_ >= 15 && log2n_ <= 20) ? 16 : (log2n_ >= 10 && log2n_ <= 12) ? 4 : 0)
-                       : ((log2n_ >= 14 && log2n_ <= 16) ? 8 : (log2n_ >= 10 && log2n_ <= 12) ? 4 : 0);
+    // 2^16 = 256 x 256 on teams of 4 (RA <= E: no larger size has two-stage sub-transforms).  Which shapes are built: the list of
+    // fft_team_quad_decl.h.
+    // (RT::team_quad_slots is optional: a runtime without the hook asks for nothing, and every shape runs the first protocol listed for it)
+    template <class R>
+    static auto quad_slots_asked(R* r, int log2n_, int log2TS, int) -> decltype(r->team_quad_slots(SZ, log2n_, log2TS)) {
+        return r->team_quad_slots(SZ, log2n_, log2TS);
     }
+    template <class R>
+    static int quad_slots_asked(R*, int, int, long) { return 0; }
     void build_team_quad(int batch) {
         const int mode = rt->policy.team_mode;
         if (mode <= 0) return;
-        const int E = quad_E(log2n);
+        const int E = fftk::quad_E<T>(log2n);
         if (!E || !rt->team_quad(SZ, log2n)) return;
         TeamDesc<T> d;
         if (!rt->team_geometry(d.log2seats, d.n_xcc, d.nthreads)) return;
@@ -327,11 +338,9 @@ class Pow2Plan {
         if (d.log2TS < 0 || d.log2TS > d.log2seats) return;
         const long long NC = L2 >> d.log2TS, NR = L1 >> d.log2TS;
         if (NC * RA != d.nthreads || NR * RB != d.nthreads || NC < 8) return;
-#if !defined(FFT_EMU)
-        if (d.log2TS != log2n - (SZ == 8 ? 15 : 14)) return;  // the device instantiations
-#else
-        if (!((log2n == 12 && d.log2TS == 2) || ((log2n == 11 || log2n == 10) && (d.log2TS == 1 || d.log2TS == 2)) || (log2n == 10 && d.log2TS == 0))) return;  // the emulation's
-#endif
+        // the protocol the runtime asks for where that is built, else the first one listed for this shape; none: this team size is not built
+        d.quad_slots = fftk::quad_slots<T>(log2n, d.log2TS, quad_slots_asked(rt, log2n, d.log2TS, 0));
+        if (!d.quad_slots) return;
         if (mode == 1 && !rt->team_default_on(SZ, log2n)) return;
         d.quad = true;
         d.E = E;
@@ -379,42 +388,12 @@ class Pow2Plan {
 
     void launch_team_quad(const fftk::TeamParams<T>& tp) {
         const long long grid = (long long)team.n_xcc << team.log2seats;
-#define FFT_QUAD_GO(...) rt->launch_coresident(fftk::team_quad_kernel<T, __VA_ARGS__>, grid, team.nthreads, (size_t)team.smem_bytes, tp)
-#if defined(FFT_EMU)
-        const bool pair = getenv("FFT_EMU_QUAD_SLOTS") && atoi(getenv("FFT_EMU_QUAD_SLOTS")) == 3 && team.log2TS >= 1;
-        if (pair && log2n == 12) FFT_QUAD_GO(4, 2, 2, 6, 6, 2, 3);  // the pair protocol (the device's n = 2^20) on teams of 4 and of 2
-        else if (pair && log2n == 11 && team.log2TS == 1) FFT_QUAD_GO(4, 2, 1, 6, 5, 1, 3);
-        else if (pair && log2n == 11) FFT_QUAD_GO(4, 2, 1, 6, 5, 2, 3);
-        else if (pair && team.log2TS == 1) FFT_QUAD_GO(4, 1, 1, 5, 5, 1, 3);
-        else if (pair) FFT_QUAD_GO(4, 1, 1, 5, 5, 2, 3);
-        else if (log2n == 12) FFT_QUAD_GO(4, 2, 2, 6, 6, 2, 2);
-        else if (log2n == 11 && team.log2TS == 1) FFT_QUAD_GO(4, 2, 1, 6, 5, 1, 2);
-        else if (log2n == 11) FFT_QUAD_GO(4, 2, 1, 6, 5, 2, 1);
-        else if (team.log2TS == 0) FFT_QUAD_GO(4, 1, 1, 5, 5, 0, 1);
-        else if (team.log2TS == 1) FFT_QUAD_GO(4, 1, 1, 5, 5, 1, 1);
-        else FFT_QUAD_GO(4, 1, 1, 5, 5, 2, 1);
-#else
-        if constexpr (SZ == 8) {
-            const int slots = rt->team_quad_slots(log2n);
-            if (log2n == 20 && slots == 3) FFT_QUAD_GO(16, 4, 4, 10, 10, 5, 3);
-            else if (log2n == 19 && slots == 3) FFT_QUAD_GO(16, 4, 3, 10, 9, 4, 3);
-            else if (log2n == 18 && slots == 3) FFT_QUAD_GO(16, 3, 3, 9, 9, 3, 3);
-            else if (log2n == 17 && slots == 3) FFT_QUAD_GO(16, 3, 2, 9, 8, 2, 3);
-            else if (log2n == 20 && slots == 1) FFT_QUAD_GO(16, 4, 4, 10, 10, 5, 1);
-            else if (log2n == 20) FFT_QUAD_GO(16, 4, 4, 10, 10, 5, 2);
-            else if (log2n == 19 && slots == 1) FFT_QUAD_GO(16, 4, 3, 10, 9, 4, 1);
-            else if (log2n == 19) FFT_QUAD_GO(16, 4, 3, 10, 9, 4, 2);
-            else if (log2n == 18 && slots == 2) FFT_QUAD_GO(16, 3, 3, 9, 9, 3, 2);
-            else if (log2n == 18) FFT_QUAD_GO(16, 3, 3, 9, 9, 3, 1);
-            else if (log2n == 17) FFT_QUAD_GO(16, 3, 2, 9, 8, 2, 1);
-            else if (log2n == 15) FFT_QUAD_GO(16, 2, 1, 8, 7, 0, 1);
-            else FFT_QUAD_GO(16, 2, 2, 8, 8, 1, 1);
-        } else {
-            if (log2n == 14) FFT_QUAD_GO(8, 3, 1, 8, 6, 0, 1);
-            else if (log2n == 15) FFT_QUAD_GO(8, 3, 2, 8, 7, 1, 1);
-            else FFT_QUAD_GO(8, 3, 3, 8, 8, 2, 1);
-        }
-#endif
+#define FFT_QUAD_GO(TT, E, RA, RB, L1, L2, TS, SLOTS)                                                                            \
+    if constexpr (std::is_same<T, TT>::value) {                                                                                  \
+        if (log2n == (L1) + (L2) && team.log2TS == (TS) && team.quad_slots == (SLOTS))                                           \
+            return rt->launch_coresident(fftk::team_quad_kernel<TT, E, RA, RB, L1, L2, TS, SLOTS>, grid, team.nthreads, (size_t)team.smem_bytes, tp); \
+    }
+        FFT_QUAD_INSTANCES(FFT_QUAD_GO)
 #undef FFT_QUAD_GO
         (void)grid;
     }
@@ -522,28 +501,21 @@ class Pow2Plan {
         team = d;
     }
 
-    template <int LOG2N>
-    void launch_team_n(const fftk::TeamParams<T>& tp) {
+    template <int GEO, bool ASPLIT, bool PAIR>  // a row of fft_team_list.h
+    void launch_team_geo(const fftk::TeamParams<T>& tp) {
         const long long grid = (long long)team.n_xcc << team.log2seats;
-        constexpr int GEO = fftk::TeamGeo<T, LOG2N>::value;
-        if (GEO == 0) return;
-        if (team.defer && team.pair && team.nodefer && team.alll2 && fftk::TeamPairBuilt<T, LOG2N>::value)
-            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, (GEO ? GEO : 1), fftk::TeamPairBuilt<T, LOG2N>::value, fftk::TeamPairBuilt<T, LOG2N>::value,
-                                                          fftk::TeamPairBuilt<T, LOG2N>::value>,
-                                  grid, team.nthreads, (size_t)team.smem_bytes, tp);
-        else if (team.defer && team.pair && team.nodefer && fftk::TeamPairBuilt<T, LOG2N>::value)
-            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, (GEO ? GEO : 1), fftk::TeamPairBuilt<T, LOG2N>::value, fftk::TeamPairBuilt<T, LOG2N>::value>,
-                                  grid, team.nthreads, (size_t)team.smem_bytes, tp);
-        else if (team.defer && team.pair && fftk::TeamPairBuilt<T, LOG2N>::value)
-            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, (GEO ? GEO : 1), fftk::TeamPairBuilt<T, LOG2N>::value>, grid, team.nthreads,
-                                  (size_t)team.smem_bytes, tp);
+        if (team.defer && team.pair && team.nodefer && team.alll2 && PAIR)
+            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, GEO, PAIR, PAIR, PAIR>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
+        else if (team.defer && team.pair && team.nodefer && PAIR)
+            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, GEO, PAIR, PAIR>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
+        else if (team.defer && team.pair && PAIR)
+            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, GEO, PAIR>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
         else if (team.defer)
-            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, (GEO ? GEO : 1)>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
-        else if (fftk::TeamAsplitBuilt<T, LOG2N>::value && team.asplit)
-            rt->launch_coresident(fftk::team_fft_kernel<T, 4, 8 * V, (GEO ? GEO : 1), fftk::TeamAsplitBuilt<T, LOG2N>::value>, grid,
-                                  team.nthreads, (size_t)team.smem_bytes, tp);
+            rt->launch_coresident(fftk::team_defer_kernel<T, 8 * V, GEO>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
+        else if (ASPLIT && team.asplit)
+            rt->launch_coresident(fftk::team_fft_kernel<T, 4, 8 * V, GEO, ASPLIT>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
         else
-            rt->launch_coresident(fftk::team_fft_kernel<T, 4, 8 * V, (GEO ? GEO : 1)>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
+            rt->launch_coresident(fftk::team_fft_kernel<T, 4, 8 * V, GEO>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
     }
 
     template <int NT>
@@ -563,16 +535,12 @@ class Pow2Plan {
             rt->launch_coresident(fftk::team_fft_kernel<T, NT, 8 * V, 0>, grid, team.nthreads, (size_t)team.smem_bytes, tp);
     }
 
-    int built_geo() const {
-        switch (log2n) {
-            case 15: return fftk::TeamGeo<T, 15>::value;
-            case 16: return fftk::TeamGeo<T, 16>::value;
-            case 17: return fftk::TeamGeo<T, 17>::value;
-            case 18: return fftk::TeamGeo<T, 18>::value;
-            case 19: return fftk::TeamGeo<T, 19>::value;
-            case 20: return fftk::TeamGeo<T, 20>::value;
-            default: return 0;
-        }
+    int built_geo() const {  // the baked-in geometry of the device instantiation for this size (fft_team_list.h); 0: none
+#define FFT_TEAM_ROW(TT, LOG2N, GEO, ASPLIT, PAIR) \
+    if (std::is_same<T, TT>::value && log2n == (LOG2N)) return GEO;
+        FFT_TEAM_INSTANCES(FFT_TEAM_ROW)
+#undef FFT_TEAM_ROW
+        return 0;
     }
 
     bool team_geometry_is_built() const {
@@ -642,14 +610,13 @@ class Pow2Plan {
             default: launch_team_emu<4>(tp); break;
         }
 #else
-        switch (log2n) {  // the device instantiations have their geometry baked in (fft_team_list.h)
-            case 15: launch_team_n<15>(tp); break;
-            case 16: launch_team_n<16>(tp); break;
-            case 17: launch_team_n<17>(tp); break;
-            case 18: launch_team_n<18>(tp); break;
-            case 19: launch_team_n<19>(tp); break;
-            default: launch_team_n<20>(tp); break;
-        }
+        // the device instantiations have their geometry baked in (fft_team_list.h; team_geometry_is_built() has matched the plan against it)
+#define FFT_TEAM_ROW(TT, LOG2N, GEO, ASPLIT, PAIR)               \
+    if constexpr (std::is_same<T, TT>::value) {                  \
+        if (log2n == (LOG2N)) return launch_team_geo<GEO, ASPLIT, PAIR>(tp); \
+    }
+        FFT_TEAM_INSTANCES(FFT_TEAM_ROW)
+#undef FFT_TEAM_ROW
 #endif
     }
 
@@ -1109,46 +1076,22 @@ class Pow2Plan {
                                  ((LM == fftk::LOAD_CCONTIG && (FAM == fftk::FAM_R4 || FAM == fftk::FAM_SR16) && TW) ||
                                   (LM == fftk::LOAD_LCONTIG && SM == fftk::STORE_CCONTIG && FAM == fftk::FAM_SR16 && !TW));
         static const int use_fixed = FFT_EXP_ENV("FFT_HIP_FIXED") ? atoi(FFT_EXP_ENV("FFT_HIP_FIXED")) : 1;
-        if (HAS_FIX && use_fixed) {
-            const int full_c = 13 - ilog2(SZ / 8) - p.log2L;  // log2 of (8192 or 4096 elements) / L
-            if (p.log2C == full_c) {
-                switch (p.log2L) {
-                    case 7: launch_fixed<E, H, FAM, LM, SM, TW, HAS_FIX, 7>(tp, grid, p); return;
-                    case 8: launch_fixed<E, H, FAM, LM, SM, TW, HAS_FIX, 8>(tp, grid, p); return;
-                    case 9: launch_fixed<E, H, FAM, LM, SM, TW, HAS_FIX, 9>(tp, grid, p); return;
-                    case 10: launch_fixed<E, H, FAM, LM, SM, TW, HAS_FIX, 10>(tp, grid, p); return;
-                    default: break;
-                }
-            }
-        }
         // ... and the single-pass rows kernel (E = 4, radix-4) for n = 128, 256 fp32 (fft_rows_list.h says why only those)
         constexpr bool ROWS_FIX = E == 4 && H == 1 && LM == fftk::LOAD_LCONTIG && SM == fftk::STORE_LCONTIG && FAM == fftk::FAM_R4 && !TW && SZ == 8;
-        if (ROWS_FIX && use_fixed && p.log2C == 13 - p.log2L) {
-            switch (p.log2L) {
-                case 7: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX, 7>(tp, grid, p); return;
-                case 8: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX, 8>(tp, grid, p); return;
-                default: break;
-            }
-        }
         // ... and its E = 8 radix-8 form, n = 512 ... 4096, fp32
         constexpr bool ROWS_FIX8 = E == 8 && H == 1 && LM == fftk::LOAD_LCONTIG && SM == fftk::STORE_LCONTIG && FAM == fftk::FAM_SR16 && !TW && SZ == 8;
-        if (ROWS_FIX8 && use_fixed && p.log2C == 13 - p.log2L) {
-            switch (p.log2L) {
-                case 9: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX8, 9>(tp, grid, p); return;
-                case 10: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX8, 10>(tp, grid, p); return;
-                case 11: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX8, 11>(tp, grid, p); return;
-                case 12: launch_fixed<E, H, FAM, LM, SM, TW, ROWS_FIX8, 12>(tp, grid, p); return;
-                default: break;
-            }
+        [[maybe_unused]] auto fixed = [&](auto l) { launch_kernel(fftk::tile_fft_kernel<T, E, H, FAM, LM, SM, TW, full_tile_fix(decltype(l)::value)>, tp, grid, p); };
+        if (use_fixed && is_full_tile(p.log2L, p.log2C)) {
+            if constexpr (HAS_FIX) { if (with_constant<7, 10>(p.log2L, fixed)) return; }
+            if constexpr (ROWS_FIX) { if (with_constant<7, 8>(p.log2L, fixed)) return; }
+            if constexpr (ROWS_FIX8) { if (with_constant<9, 12>(p.log2L, fixed)) return; }
         }
         launch_kernel(fftk::tile_fft_kernel<T, E, H, FAM, LM, SM, TW, 0>, tp, grid, p);
     }
 
-    template <int E, int H, int FAM, int LM, int SM, bool TW, bool HAS_FIX, int LOG2L>
-    void launch_fixed(const fftk::TileParams<T>& tp, long long grid, const PassDesc& p) {
-        constexpr int FIX = HAS_FIX ? ((LOG2L << 8) | (13 - (SZ == 16 ? 1 : 0) - LOG2L)) : 0;
-        launch_kernel(fftk::tile_fft_kernel<T, E, H, FAM, LM, SM, TW, FIX>, tp, grid, p);
-    }
+    // the FIX template argument of the tile kernels for the full 64 KiB tile with its shape baked in: (log2 L << 8) | log2 C, L C = 8192 (fp32) / 4096 (fp64)
+    static constexpr int full_tile_fix(int log2L) { return (log2L << 8) | (13 - (SZ == 16 ? 1 : 0) - log2L); }
+    static constexpr bool is_full_tile(int log2L, int log2C) { return ((log2L << 8) | log2C) == full_tile_fix(log2L); }
 
     template <class K>
     void launch_kernel(K kernel, const fftk::TileParams<T>& tp, long long grid, const PassDesc& p) {
@@ -1290,19 +1233,12 @@ class Pow2Plan {
     void launch_hooked_fixed(const fftk::TileParams<T>& tp, const PassDesc& p) {
         using namespace fftk;
         static const int use_fixed = FFT_EXP_ENV("FFT_HIP_FIXED") ? atoi(FFT_EXP_ENV("FFT_HIP_FIXED")) : 1;
-        constexpr int D = SZ == 16 ? 1 : 0;
         // (the fp64 store-hooked row pass spills 23...42 VGPRs with its shape baked in: generic there)
         constexpr bool FIX_OK = !(SZ == 16 && (HOOK & 2));
         if constexpr (FIX_OK) {
-          if (use_fixed && p.log2C == 13 - D - p.log2L) {
-            switch (p.log2L) {
-                case 7: launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, (7 << 8) | (13 - D - 7), HOOK>, tp, -1, p); return;
-                case 8: launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, (8 << 8) | (13 - D - 8), HOOK>, tp, -1, p); return;
-                case 9: launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, (9 << 8) | (13 - D - 9), HOOK>, tp, -1, p); return;
-                case 10: launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, (10 << 8) | (13 - D - 10), HOOK>, tp, -1, p); return;
-                default: break;
-            }
-          }
+            if (use_fixed && is_full_tile(p.log2L, p.log2C) &&
+                with_constant<7, 10>(p.log2L, [&](auto l) { launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, full_tile_fix(decltype(l)::value), HOOK>, tp, -1, p); }))
+                return;
         }
         launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, 0, HOOK>, tp, -1, p);
     }
@@ -1393,17 +1329,10 @@ class Pow2Plan {
         k.post_tab_b = h.post_tab_b;
         k.post_mode = (h.post_tab || h.post_mode == HOOK_ABS2) ? h.post_mode : HOOK_NONE;
         // the full 64 KiB tile of L in {128 ... 1024} gets an instantiation with L and C baked in (as launch_one_h does)
-        const int full_c = 13 - ilog2(SZ / 8) - a.log2L;
         static const int use_fixed = FFT_EXP_ENV("FFT_HIP_FIXED") ? atoi(FFT_EXP_ENV("FFT_HIP_FIXED")) : 1;
-        if (use_fixed && a.log2C == full_c) {
-            switch (a.log2L) {
-                case 7: launch_chain_kernel(tile_fft_ba_kernel<T, ((7 << 8) | (13 - (SZ == 16 ? 1 : 0) - 7))>, q, a.nthreads); return;
-                case 8: launch_chain_kernel(tile_fft_ba_kernel<T, ((8 << 8) | (13 - (SZ == 16 ? 1 : 0) - 8))>, q, a.nthreads); return;
-                case 9: launch_chain_kernel(tile_fft_ba_kernel<T, ((9 << 8) | (13 - (SZ == 16 ? 1 : 0) - 9))>, q, a.nthreads); return;
-                case 10: launch_chain_kernel(tile_fft_ba_kernel<T, ((10 << 8) | (13 - (SZ == 16 ? 1 : 0) - 10))>, q, a.nthreads); return;
-                default: break;
-            }
-        }
+        if (use_fixed && is_full_tile(a.log2L, a.log2C) &&
+            with_constant<7, 10>(a.log2L, [&](auto l) { launch_chain_kernel(tile_fft_ba_kernel<T, full_tile_fix(decltype(l)::value)>, q, a.nthreads); }))
+            return;
         launch_chain_kernel(tile_fft_ba_kernel<T, 0>, q, a.nthreads);
     }
     template <class K>

@@ -171,24 +171,28 @@ struct HipRT {
         static const int on = FFT_EXP_ENV("FFT_HIP_TEAM_PAIR") ? atoi(FFT_EXP_ENV("FFT_HIP_TEAM_PAIR")) : FFT_TEAM_PAIR_DEFAULT;
         return on && elem_bytes == 8 && (log2n == 19 || log2n == 20);
     }
-    // team_quad_kernel (fft_team_quad.h) instead of the tile-by-tile team kernels: fp32 n = 2^15 .. 2^20.  FFT_HIP_TEAM_QUAD (the
-    // experiments build): 0 never, 1 every built size (default), or a bit mask: bit (log2n - 14) = that size only
-    bool team_quad(int elem_bytes, int log2n) {
+    // team_quad_kernel (fft_team_quad.h) instead of the tile-by-tile team kernels, at the sizes it is built for (fft_team_quad_decl.h; the planner
+    // asks for those only).  FFT_HIP_TEAM_QUAD (the experiments build): 0 never, 1 every built size (default), or a bit mask: bit (log2n - 14) =
+    // that size only
+    bool team_quad(int /*elem_bytes*/, int log2n) {
         static const int on = FFT_EXP_ENV("FFT_HIP_TEAM_QUAD") ? atoi(FFT_EXP_ENV("FFT_HIP_TEAM_QUAD")) : 1;
-        if (elem_bytes == 8 ? (log2n < 15 || log2n > 20) : (log2n < 14 || log2n > 16)) return false;
         if (on <= 1) return on == 1;
         return (on >> (log2n - 14)) & 1;
     }
-    // the exchange protocol of team_quad_kernel where several are built (n = 2^17 ... 2^20): window slots 1 / 2 with the team's arrival counter,
-    // 3 = one image per seat with the pair protocol (the experiments build: FFT_HIP_QUAD_SLOTS=1 / 2 / 3)
-    int team_quad_slots(int log2n) {
+    // the exchange protocol of team_quad_kernel to ask for: window slots 1 / 2 with the team's arrival counter, 3 = one image per seat with the pair
+    // protocol.  The planner falls back where that one is not built for the size.  The experiments build: FFT_HIP_QUAD_SLOTS=1 / 2 / 3 (any other
+    // value counts as unset)
+    int team_quad_slots(int elem_bytes, int log2n, int /*log2TS*/) {
         static const int v = FFT_EXP_ENV("FFT_HIP_QUAD_SLOTS") ? atoi(FFT_EXP_ENV("FFT_HIP_QUAD_SLOTS")) : 0;
-        return v ? v : (log2n == 20 ? FFT_QUAD_SLOTS20 : log2n == 19 ? FFT_QUAD_SLOTS19 : log2n == 18 ? FFT_QUAD_SLOTS18 : log2n == 17 ? FFT_QUAD_SLOTS17 : 1);
+        if (v >= 1 && v <= 3) return v;
+        if (elem_bytes != 8) return 1;
+        return log2n == 20 ? FFT_QUAD_SLOTS20 : log2n == 19 ? FFT_QUAD_SLOTS19 : log2n == 18 ? FFT_QUAD_SLOTS18 : log2n == 17 ? FFT_QUAD_SLOTS17 : 1;
     }
-    // wide_row_kernel (fft_wide_row.h): single-pass n = 8192 and 16384 fp32.  FFT_HIP_WIDE=0 (the experiments build): the two-pass schedule
-    bool wide_rows(int elem_bytes, int log2n) {
+    // wide_row_kernel (fft_wide_row.h, which lists the sizes) for single-pass n = 8192 and 16384.  FFT_HIP_WIDE=0 (the experiments build): the
+    // two-pass schedule
+    bool wide_rows(int /*elem_bytes*/, int /*log2n*/) {
         static const int on = FFT_EXP_ENV("FFT_HIP_WIDE") ? atoi(FFT_EXP_ENV("FFT_HIP_WIDE")) : 1;
-        return on && gfx950 && ((elem_bytes == 8 && (log2n == 13 || log2n == 14)) || (elem_bytes == 16 && log2n == 13));
+        return on && gfx950;
     }
     bool team_alll2(int, int) {
         static const int on = FFT_EXP_ENV("FFT_HIP_TEAM_ALLL2") ? atoi(FFT_EXP_ENV("FFT_HIP_TEAM_ALLL2")) : 0;

@@ -1,5 +1,5 @@
-// fft_team_quad.hip -- the device instantiations of team_quad_kernel (fft_team_quad.h): fp32, E = 16 values per thread and chunk,
-// 512-thread workgroups, one per CU.
+// fft_team_quad.hip -- the device instantiations of team_quad_kernel (fft_team_quad.h; the list: fft_team_quad_decl.h) and of
+// wide_row_kernel (fft_wide_row.h, with its list): 512-thread workgroups, one per CU.
 #include "fft_team_quad.h"
 #include "fft_wide_row.h"
 
@@ -7,7 +7,7 @@ namespace fftk {
 #define FFT_QUAD_DEFINE(T, ...) template __global__ void team_quad_kernel<T, __VA_ARGS__>(TeamParams<T>);
 FFT_QUAD_INSTANCES(FFT_QUAD_DEFINE)
 #undef FFT_QUAD_DEFINE
-template __global__ void wide_row_kernel<float, 13>(WideParams<float>);  // single-pass n = 8192 (fft_wide_row.h)
-template __global__ void wide_row_kernel<float, 14>(WideParams<float>);  // single-pass n = 16384
-template __global__ void wide_row_kernel<double, 13, 16>(WideParams<double>);  // fp64 n = 8192: 512 threads, one 128 KiB image in place
+#define FFT_WIDE_DEFINE(T, LOG2L, E) template __global__ void wide_row_kernel<T, LOG2L, E>(WideParams<T>);
+FFT_WIDE_INSTANCES(FFT_WIDE_DEFINE)
+#undef FFT_WIDE_DEFINE
 }

@@ -9,6 +9,8 @@
 // Reference shape: the stage loop of algorithms/core/radix2_dit.c:84-112 with its intermediate stages held in LDS.
 #pragma once
 
+#include <type_traits>
+
 #include "fft_team.h"
 
 namespace fftk {
@@ -125,5 +127,30 @@ FFT_KERNEL void FFT_WIDE_BOUNDS(LOG2L, E) wide_row_kernel(WideParams<T> p) {
     }
 }
 #endif
+
+// THE list of built shapes, <T, log2 n, E>: the instantiations (fft_team_quad.hip), their extern declarations where the body is not included
+// (FFT_WIDE_DECL_ONLY), the sizes the planner plans (wide_row_E) and its dispatch (Pow2Plan::launch_wide).  A new instantiation is one row.
+#if defined(FFT_EMU)
+#define FFT_WIDE_INSTANCES(X) X(float, 9, 16) /* n = 512 on 32 threads */
+#else
+#define FFT_WIDE_INSTANCES(X)                                                       \
+    X(float, 13, 16)  /* single-pass n = 8192 */                                    \
+    X(float, 14, 16)  /* single-pass n = 16384 */                                   \
+    X(double, 13, 16) /* fp64 n = 8192: 512 threads, one 128 KiB image in place */
+#endif
+#if defined(FFT_WIDE_DECL_ONLY)
+#define FFT_WIDE_EXTERN(T, LOG2L, E) extern template __global__ void wide_row_kernel<T, LOG2L, E>(WideParams<T>);
+FFT_WIDE_INSTANCES(FFT_WIDE_EXTERN)
+#undef FFT_WIDE_EXTERN
+#endif
+// values per thread of the kernel built for <T, log2 n>; 0: none
+template <typename T>
+constexpr int wide_row_E(int log2n) {
+#define FFT_WIDE_ROW(TT, LOG2L, E) \
+    if (std::is_same<T, TT>::value && log2n == (LOG2L)) return E;
+    FFT_WIDE_INSTANCES(FFT_WIDE_ROW)
+#undef FFT_WIDE_ROW
+    return 0;
+}
 
 }  // namespace fftk

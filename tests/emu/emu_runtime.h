@@ -51,8 +51,15 @@ struct Runtime {
     bool team_default_on(int, int) { return true; }
     bool team_defer(int, int) { return getenv("FFT_EMU_TEAM_PLAIN") == nullptr; }  // the shipped default; FFT_EMU_TEAM_PLAIN: team_fft_kernel
     bool team_asplit(int, int) { return getenv("FFT_EMU_TEAM_ASPLIT") != nullptr; }
-    bool team_quad(int, int log2n) { return (log2n >= 10 && log2n <= 12) && getenv("FFT_EMU_TEAM_QUAD") != nullptr; }
-    bool wide_rows(int elem_bytes, int log2n) { return elem_bytes == 8 && log2n == 9 && getenv("FFT_EMU_WIDE") != nullptr; }
+    bool team_quad(int, int) { return getenv("FFT_EMU_TEAM_QUAD") != nullptr; }
+    // team_quad_kernel's exchange protocol: FFT_EMU_QUAD_SLOTS=3 asks for the pair protocol (the planner falls back where a shape has none: teams of
+    // one seat); else the emulated shape's default -- two window slots at n = 2^12 and on the teams of 2 at 2^11, one elsewhere
+    int team_quad_slots(int, int log2n, int log2TS) {
+        const char* e = getenv("FFT_EMU_QUAD_SLOTS");
+        if (e && atoi(e) == 3) return 3;
+        return (log2n == 12 || (log2n == 11 && log2TS == 1)) ? 2 : 1;
+    }
+    bool wide_rows(int, int) { return getenv("FFT_EMU_WIDE") != nullptr; }
     bool team_alll2(int, int) { return getenv("FFT_EMU_TEAM_ALLL2") != nullptr; }
     bool team_nodefer(int, int) { return getenv("FFT_EMU_TEAM_NODEFER") != nullptr; }
     bool team_pair(int elem_bytes, int) { return elem_bytes == 8 && getenv("FFT_EMU_TEAM_PAIR") != nullptr; }

@@ -901,3 +901,39 @@ def test_team_kernel_even_odd_row_split(gpu_lib, monkeypatch):
                FFT_LIB_PATH=os.path.join(ROOT, "fft-implementation-in-c_amd", "libfft_mi355x_exp.so"))
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "ok" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.parametrize("log2n,slots", [(20, "1"), (20, "2"), (19, "1"), (19, "2"), (18, "1"), (18, "2"), (17, "3")])
+def test_team_quad_kernel_experiments_only_protocols(gpu_lib, log2n, slots):
+    """The rows of team_quad_kernel's list (fft_team_quad_decl.h) that no default policy launches: FFT_HIP_QUAD_SLOTS=1 / 2 (one / two window
+    slots with the team's arrival counter) where the pair protocol is the default (fp32 n = 2^18 ... 2^20), and the pair protocol (3) at 2^17,
+    which stays on the counter.  One transform more than there are teams: a ragged last round, and the smallest batch in which a team claims
+    a second transform from the device-wide counter.  Forward and inverse, every transform bin by bin.  The switch is read once per process,
+    hence the fresh one."""
+    import subprocess
+    import sys
+    code = (
+        "import os, sys, numpy as np\n"
+        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import fftlib, oracle_lib as O, accuracy as A\n"
+        "fftlib.init()\n"
+        "log2n = %d\n"
+        "n, batch = 1 << log2n, (8 << (20 - log2n)) + 1\n"
+        "x = O.gen_lcg(n, 47, batch).astype(np.complex64)\n"
+        "buf = fftlib.DeviceBuffer(x.nbytes); out = fftlib.DeviceBuffer(x.nbytes)\n"
+        "for d in (-1, 1):\n"
+        "    p = fftlib.Plan(n, batch, d, np.complex64)\n"
+        "    assert p.info().team_kernel == 3, p.info().team_kernel\n"
+        "    buf.upload(x); out.upload(np.full_like(x, np.nan))\n"
+        "    p.execute_ptr(buf.ptr, out.ptr)\n"
+        "    assert p.team_status() == 0\n"
+        "    A.check_rows(out.download(x.shape, np.complex64), x, d, 'team_quad', label='2^%%d slots %s' %% log2n)\n"
+        "    p.destroy()\n"
+        "buf.free(); out.free()\n"
+        "print('ok')\n"
+    ) % (os.path.join(ROOT, "fft-implementation-in-c_amd"), os.path.join(ROOT, "tests"), log2n, slots)
+    # kernel-variant switches exist only in the -DFFT_EXPERIMENTS build of the library
+    env = dict(os.environ, FFT_HIP_TEAM="2", FFT_HIP_QUAD_SLOTS=slots,
+               FFT_LIB_PATH=os.path.join(ROOT, "fft-implementation-in-c_amd", "libfft_mi355x_exp.so"))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "ok" in out.stdout, out.stdout + out.stderr
