@@ -1242,6 +1242,29 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->f32) fill_fused(p->f32);
     if (p->f64) fill_fused(p->f64);
+    // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
+    auto fill_any = [&](auto* a) {
+        if (a->p2) fill(a->p2);
+        if (a->bl) {
+            fill(&a->bl->core);
+            info->bluestein_m = 1 << a->bl->log2m;
+        }
+    };
+    auto fill_real = [&](auto* r) { fill_any(&r->core); };  // r2c / c2r: the half-length (even n) or full-length complex core
+    if (p->r32) fill_real(p->r32);
+    if (p->r64) fill_real(p->r64);
+    // 2D: algo, chunk_batch, bluestein_m describe the row transforms; n_passes / factors the strided column passes
+    // (1 direct, 2 two strided passes, 0: columns on the transposed image, or a single row)
+    auto fill_2d = [&](auto* d) {
+        fill_any(&d->rowp);
+        info->n_passes = d->colp ? (int)d->colp->passes.size() : 0;
+        for (int i = 0; i < 4; i++) info->factors[i] = 0;
+        if (d->colp)
+            for (size_t i = 0; i < d->colp->passes.size() && i < 4; i++) info->factors[i] = 1 << d->colp->passes[i].log2L;
+        if (d->tbuf) info->workspace_bytes += (size_t)d->rows * (size_t)d->cols * (size_t)d->max_matrices * sizeof(*d->tbuf);
+    };
+    if (p->d32) fill_2d(p->d32);
+    if (p->d64) fill_2d(p->d64);
     return 0;
 }
 

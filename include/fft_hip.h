@@ -96,6 +96,10 @@ typedef struct {
     int team_kernel;    /* which one-round-trip kernel team_tiles refers to: 0 none, 1 team_fft_kernel (csrc/fft_team.h), 2
                            team_defer_kernel (csrc/fft_team_defer.h), 3 team_quad_kernel (csrc/fft_team_quad.h: whole-line row
                            segments, both steps decimated by 4, the exchange in four rounds through the XCD's L2) */
+    /* r2c / c2r plans: algo ... team_kernel describe the complex core (length n/2 for even n, n for odd n).
+       2D plans: algo, chunk_batch, bluestein_m, team_* describe the row transforms (length cols); n_passes and factors the
+       strided column passes: 1 the direct column pass, 2 two strided passes, 0 the columns run on the transposed image
+       (or rows == 1: there are none). */
 } fft_gpu_plan_info_t;
 
 /* Per-plan switches (tests and integrators; nothing here changes results) */

@@ -17,6 +17,13 @@ check_execute() runs a batch through a raw-pointer execute into a NaN-filled out
 sentinel pattern, and checks every transform, the guards, the untouched input of an out-of-place execute and the bit identity of
 the in-place result with the out-of-place one.
 
+check_execute_io() is the same for executes whose input and output rows differ in width or type (2D, r2c / c2r, the fused
+consumers; an optional second input): every buffer has guards of its own size.  The fused families measure bin k's error in units
+of max(RMS_b, |X[b, k]|) (row_errors(scale="rms_or_bin")): a correlation's lag 0 is ~ n sigma^2 where the other lags are
+~ sqrt(n) sigma^2, so the peak's own rounding error, in units of the row's RMS, grows like sqrt(n) and says nothing about the
+kernel (CPU emulation, autocorrelation of nx = 4095, RMS units: 18.4 / 16.2 u log2 m; nx = 100: about 3); a periodogram's bins are
+exponentially distributed and show the same, milder.  A wrong bin, a neighbour's value or swapped rows still fail.
+
 The measured columns of the K tables below come from a GPU-suite run with FFT_ACCURACY_REPORT=<file>: at exit every process
 merges the worst e_b / (u log2 n) it saw per family and precision into that JSON file.
 """
@@ -40,7 +47,8 @@ U = {np.dtype(np.complex64): 2.0 ** -24, np.dtype(np.complex128): 2.0 ** -53,
      np.dtype(np.float32): 2.0 ** -24, np.dtype(np.float64): 2.0 ** -53}
 
 # K of the bound K * u * log2(n) per path family, and the worst e_b / (u * log2 n) measured on the MI355X over the GPU suite
-# (fp32 / fp64).  Each K is at least twice the worst measured value; caps: 16 for the power-of-two paths, 64 for Bluestein.
+# (fp32 / fp64).  Each K is at least twice the worst measured value; caps: 16 for the power-of-two paths (r2c, c2r and 2d among
+# them), 64 for Bluestein and for the fused families, which have its structure: two transforms of length m with a product between.
 BOUND_K = {
     "multipass": 8,    # multi-pass and single-pass schedules (csrc/fft_kernels.h)       measured 2.16 (2^4) / 2.58 (2^4)
     "radix2_global": 8,  # bitrev_kernel + radix2_dit_stage_kernel, one launch per stage   measured 1.98 (2^6) / 2.06 (2^3)
@@ -51,6 +59,12 @@ BOUND_K = {
     "bluestein": 32,   # chirp-z over a power-of-two core of length m                     measured 1.81 (1000) / 2.41 (100003)
     "r2c": 8,          # r2c / c2r on a half-length complex transform                     measured 1.50 (1009) / 1.58 (1000)
     "2d": 8,           # rows + strided columns, log2(rows * cols)                         measured 0.78 / 0.80 (256 x 512)
+    # the families below: worst over the emulated cases of tests/ext_ladder.py (tests/test_emulated_ext.py), fp32 / fp64, as merged in
+    # profiles/ext_accuracy_report.json; r2c and 2d there: 1.77 / 2.69 (n = 6) and 1.49 (33 x 33) / 1.10 (12 x 32)
+    "c2r": 8,          # c2r_merge_kernel + half-length inverse (odd n: extend + full length)      measured 1.94 (9) / 2.60 (1006)
+    "fused_conv": 8,   # linear / circular convolution, log2(m); error / max(RMS, |bin|)           measured 1.20 (circular 2048) / 1.21 (99 + 27)
+    "fused_corr": 8,   # auto- / cross-correlation, log2(m); error / max(RMS, |bin|)               measured 1.81 (1500) / 1.25 (1500)
+    "psd": 8,          # Hann periodogram, log2(nx); error / max(RMS, |bin|)                       measured 0.74 (1024) / 2.07 (64)
 }
 # Two-tone inputs (oracle_lib.gen_two_tone: all the energy in two bins) against their analytic spectrum.  On them the device's
 # worst bin is NOT bounded by K u log2(n): twiddles formed as powers of one table value (quad_stage1 / quad_twiddle_kb in
@@ -61,7 +75,7 @@ TWO_TONE_K = {
     "multipass": 0.25,  # measured 0.121 (2^16, config 2 in chunks of 256)
     "team_quad": 1.0,   # measured 0.461 (worst of 2^16, 2^18, 2^20: at 2^18)
 }
-CAP = {"bluestein": 64}
+CAP = {"bluestein": 64, "fused_conv": 64, "fused_corr": 64, "psd": 64}
 POW2_CAP = 16
 
 # worst measured e_b / (u * log2 n) per (family, precision) in this process; FFT_ACCURACY_REPORT=<file> writes it out as JSON
@@ -191,21 +205,30 @@ def fft_ref_long(x, direction):
     return np.fft.fft(x, axis=-1) if direction < 0 else np.fft.ifft(x, axis=-1)
 
 
-def row_errors(y, X):
-    """e_b of every row, and the bin of each row's worst error.  y: result rows (any precision), X: reference rows."""
+def row_errors(y, X, scale="rms"):
+    """e_b of every row, and the bin of each row's worst error.  y: result rows (any precision), X: reference rows.
+    scale="rms" (default): every bin's error in units of the row's RMS bin magnitude.  scale="rms_or_bin": bin k's error in
+    units of max(RMS_b, |X[b, k]|) -- for rows with a few bins far above the rest (the lag 0 of a correlation, the peaks of a
+    periodogram), whose own rounding error would otherwise be charged in units of the small bins."""
     y = np.asarray(y)
     X = np.asarray(X)
     d = np.abs(y.astype(X.dtype) - X)
-    scale = np.sqrt(np.mean(np.abs(X) ** 2, axis=-1))
+    rms = np.maximum(np.sqrt(np.mean(np.abs(X) ** 2, axis=-1)), 1e-300)
     finite = np.all(np.isfinite(y.view(y.real.dtype) if np.iscomplexobj(y) else y).reshape(y.shape[0], -1), axis=-1)
     d = np.where(np.isnan(d), np.inf, d)
+    if scale == "rms_or_bin":
+        d = d / np.maximum(rms[:, None], np.abs(X))
+    elif scale != "rms":
+        raise ValueError("scale: 'rms' or 'rms_or_bin'")
     k = np.argmax(d, axis=-1)
     worst = d[np.arange(d.shape[0]), k]
-    e = np.where(finite, worst / np.maximum(scale, 1e-300), np.inf).astype(np.float64)
+    if scale == "rms":
+        worst = worst / rms
+    e = np.where(finite, worst, np.inf).astype(np.float64)
     return e, k
 
 
-def errors_vs(y, x, direction, ref=None, b0=0, rows_per_task=None):
+def errors_vs(y, x, direction, ref=None, b0=0, rows_per_task=None, scale="rms"):
     """e_b and worst bins of the rows y against ref(x rows) (default: the complex transform of x in `direction`), computed
     in row chunks on WORKERS threads (numpy and scipy release the GIL on whole arrays)."""
     nrows = y.shape[0]
@@ -218,7 +241,7 @@ def errors_vs(y, x, direction, ref=None, b0=0, rows_per_task=None):
     k = np.empty(nrows, dtype=np.int64)
 
     def one(s):
-        e[s:s + step], k[s:s + step] = row_errors(y[s:s + step], ref(x[s:s + step]))
+        e[s:s + step], k[s:s + step] = row_errors(y[s:s + step], ref(x[s:s + step]), scale)
 
     with ThreadPoolExecutor(WORKERS) as ex:
         list(ex.map(one, range(0, nrows, step)))
@@ -245,14 +268,15 @@ def assert_within(e, k, limit, label, b0=0):
            " ..." if bad.size > 12 else "", q[0], q[1], q[2], q[3], int(e.size - fin.size)))
 
 
-def check_rows(y, x, direction, family, dtype=None, n=None, m=None, label="", ref=None, b0=0, long_rows=0):
+def check_rows(y, x, direction, family, dtype=None, n=None, m=None, label="", ref=None, b0=0, long_rows=0, scale="rms"):
     """Check result rows y of input rows x against the reference: e_b <= bound(family) for every row.  Returns e.
+    scale: the unit of a bin's error, see row_errors().
     long_rows > 0 (fp64 results): also compare the first rows with a long-double reference, and show that the float64
     reference's own error is below a quarter of the bound."""
     dtype = np.dtype(dtype or y.dtype)
     n = n or y.shape[-1]
     lim = bound(family, dtype, n, m)
-    e, k = errors_vs(y, x, direction, ref)
+    e, k = errors_vs(y, x, direction, ref, scale=scale)
     _note(family, dtype, n, m, e)
     assert_within(e, k, lim, "%s %s n=%d dir=%+d" % (label, family, n, direction), b0)
     if long_rows and ref is None:
@@ -325,13 +349,18 @@ def _slice_rows(row_bytes):
 
 class Guarded:
     """`rows` rows of `row_bytes` bytes with one guard row of SENTINEL words before and one after, in one allocation.
-    ptr = the first payload row; with row_bytes >= 16 it keeps the allocation's 16-byte alignment."""
+    ptr = the first payload row; with row_bytes >= 16 it keeps the allocation's 16-byte alignment.
+    align16=True (rows of any width, check_execute_io): each guard is the smallest multiple of 16 bytes >= one row, so that
+    the payload starts 16-byte aligned, like a plain allocation's, whatever row_bytes is; the trailing guard starts right
+    behind the last payload byte."""
 
-    def __init__(self, rows, row_bytes):
+    def __init__(self, rows, row_bytes, align16=False):
+        assert row_bytes % 4 == 0 and row_bytes > 0
         self.rows, self.row_bytes = rows, row_bytes
-        self.base, self.handle = memory().alloc((rows + 2) * row_bytes)
-        self.ptr = self.base + row_bytes
-        g = np.full(row_bytes // 4, SENTINEL, dtype=np.uint32)
+        self.guard_bytes = -(-row_bytes // 16) * 16 if align16 else row_bytes
+        self.base, self.handle = memory().alloc(rows * row_bytes + 2 * self.guard_bytes)
+        self.ptr = self.base + self.guard_bytes
+        g = np.full(self.guard_bytes // 4, SENTINEL, dtype=np.uint32)
         h2d(self.base, g)
         h2d(self.ptr + rows * row_bytes, g)
 
@@ -349,7 +378,7 @@ class Guarded:
         return d2h(self.ptr + r0 * self.row_bytes, (cnt, width), dtype)
 
     def guards_intact(self):
-        w = self.row_bytes // 4
+        w = self.guard_bytes // 4
         a = d2h(self.base, (w,), np.uint32)
         b = d2h(self.ptr + self.rows * self.row_bytes, (w,), np.uint32)
         return bool(np.all(a == SENTINEL) and np.all(b == SENTINEL))
@@ -510,5 +539,95 @@ def check_execute(plan, x, family, direction=None, inplace=True, m=None, label="
         return e
     finally:
         for g in (gin, gout, gip):
+            if g is not None:
+                g.free()
+
+
+def _flat_rows(ptr, r0, cnt, dtype, width):
+    """Rows r0 .. r0 + cnt - 1 of a packed [rows][width] array of dtype that starts at ptr."""
+    return d2h(ptr + r0 * width * np.dtype(dtype).itemsize, (cnt, width), dtype)
+
+
+def check_execute_io(run, x, w_out, dtype_out, family, ref, x2=None, n=None, m=None, scale="rms", inplace=False, label="",
+                     expect=None, expected=None):
+    """check_execute() for executes whose input and output rows differ in width or type (2D, r2c, c2r, fused consumers).
+      x: input rows [batch][w_in]; x2: optional second input of the same shape (cross-correlation's y);
+      run(in_ptr, in2_ptr, out_ptr): enqueue the execute and wait for it (in2_ptr is None without x2);
+      ref(xs) -- ref(xs, x2s) with a second input -- the float64 reference [rows][w_out] of a slice of input rows;
+      expected: the whole reference [batch][w_out], computed once by the caller (several variants of one plan), instead of ref;
+      n / m: the length the bound K u log2(.) is taken at (default: the wider of the two rows); scale: see row_errors().
+    Inputs and output each live in a Guarded of their own row size (guards a multiple of 16 bytes, so every payload starts where
+    a plain allocation's would: 16-byte aligned, its rows packed).  Checked:
+      - the NaN-filled output: every row's e_b <= bound(family), so no row keeps a NaN;
+      - the guards of the output and of every input still hold the sentinel; the inputs are unchanged byte for byte;
+      - inplace=True: the same execute with in_ptr == out_ptr on ONE buffer of batch * max(input row, output row) bytes, the
+        input rows packed at its start (as r2c / c2r in place need it; equal rows: plainly in place): guards intact, result
+        bit-identical to the out-of-place one;
+      - expect() after every run.
+    Returns e of the out-of-place run."""
+    x = np.ascontiguousarray(x)
+    batch, w_in = x.shape
+    dt_out = np.dtype(dtype_out)
+    rb_in, rb_out = w_in * x.dtype.itemsize, w_out * dt_out.itemsize
+    n = n or max(w_in, w_out)
+    if x2 is not None:
+        x2 = np.ascontiguousarray(x2)
+        assert x2.shape == x.shape and x2.dtype == x.dtype
+    if expected is not None:
+        assert expected.shape == (batch, w_out)
+        xx, ref_rows = expected, (lambda r: r)
+    elif x2 is not None:
+        xx = np.concatenate([x, x2], axis=1)  # one array of input rows for the sliced reference
+        ref_rows = lambda r: ref(r[:, :w_in], r[:, w_in:])
+    else:
+        xx, ref_rows = x, ref
+    nan_row = np.full(w_out, np.nan, dtype=dt_out)
+    gin, gout = Guarded(batch, rb_in, align16=True), Guarded(batch, rb_out, align16=True)
+    gin2 = Guarded(batch, rb_in, align16=True) if x2 is not None else None
+    gip = None
+    try:
+        upload_rows(gin, x)
+        if gin2:
+            upload_rows(gin2, x2)
+        gout.fill(nan_row)
+        run(gin.ptr, gin2.ptr if gin2 else None, gout.ptr)
+        if expect:
+            expect()
+        assert gout.guards_intact(), "%s: out-of-place execute wrote outside [out, out + batch * %d)" % (label, w_out)
+        assert gin.guards_intact(), "%s: out-of-place execute wrote next to its input" % label
+        assert input_unchanged(gin, x), "%s: out-of-place execute changed its input" % label
+        if gin2:
+            assert gin2.guards_intact(), "%s: out-of-place execute wrote next to its second input" % label
+            assert input_unchanged(gin2, x2), "%s: out-of-place execute changed its second input" % label
+        step = max(1, _slice_rows(16 * max(w_out, xx.shape[1])))
+        es = []
+        for r0 in range(0, batch, step):
+            cnt = min(step, batch - r0)
+            y = gout.rows_at(r0, cnt, dt_out, w_out)
+            es.append(check_rows(y, xx[r0:r0 + cnt], 0, family, dt_out, n=n, m=m, label=label + " out-of-place", ref=ref_rows, b0=r0,
+                                 scale=scale))
+        e = np.concatenate(es)
+        gin.free()
+        gin = None
+        if inplace:
+            assert x2 is None
+            rb = max(rb_in, rb_out)
+            gip = Guarded(batch, rb, align16=True)
+            gip.fill(np.frombuffer(np.full(rb // 4, np.nan, dtype=np.float32).tobytes(), dtype=np.uint8))
+            h2d(gip.ptr, x)  # input rows packed at the start of the buffer
+            run(gip.ptr, None, gip.ptr)
+            if expect:
+                expect()
+            assert gip.guards_intact(), "%s: in-place execute wrote outside its buffer" % label
+            for r0 in range(0, batch, step):
+                cnt = min(step, batch - r0)
+                a = _flat_rows(gip.ptr, r0, cnt, dt_out, w_out)
+                b = gout.rows_at(r0, cnt, dt_out, w_out)
+                if not np.array_equal(a.view(np.uint8), b.view(np.uint8)):
+                    diff = np.flatnonzero(np.any(a.view(np.uint8).reshape(cnt, -1) != b.view(np.uint8).reshape(cnt, -1), axis=1))
+                    raise AssertionError("%s: in-place result differs from the out-of-place one at row %d" % (label, r0 + int(diff[0])))
+        return e
+    finally:
+        for g in (gin, gin2, gout, gip):
             if g is not None:
                 g.free()

@@ -84,8 +84,9 @@ def test_bound_table_within_caps():
     for fam, k in A.BOUND_K.items():
         assert 0 < k <= A.CAP.get(fam, A.POW2_CAP), fam
     assert A.CAP["bluestein"] <= 64 and A.POW2_CAP <= 16
+    assert set(A.CAP) == {"bluestein", "fused_conv", "fused_corr", "psd"} and all(c <= 64 for c in A.CAP.values())
     for fam in A.BOUND_K:
-        if fam != "bluestein":
+        if fam not in A.CAP:  # the families capped at POW2_CAP
             assert A.bound(fam, np.complex64, 1 << 20) < 2e-5, fam
     assert A.bound("bluestein", np.complex128, 1000003, m=1 << 21) == A.BOUND_K["bluestein"] * 2.0 ** -53 * 21  # log2(m), not log2(n)
 
@@ -297,3 +298,128 @@ def test_block_rows_are_regenerable():
     assert not np.array_equal(a[:R], A.block_normal_rows(n, 0, R, dt, seed=10))
     c = A.block_normal_rows(4096, 0, 300, np.complex128, seed=2)
     assert np.array_equal(c[123:201], A.block_normal_rows(4096, 123, 78, np.complex128, seed=2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# check_execute_io on host memory: executes whose input and output rows differ in width and type
+# ---------------------------------------------------------------------------------------------------------------------------
+IO_BATCH = 7
+IO_SHAPES = {
+    # name: (input dtype, w_in, output dtype, w_out, float64 reference of input rows)
+    "truncated": (np.complex64, 40, np.complex64, 25, lambda x: np.fft.fft(x.astype(np.complex128), axis=1)[:, :25]),     # w_out < w_in, odd pitch
+    "padded": (np.complex128, 25, np.complex128, 40, lambda x: np.fft.fft(x.astype(np.complex128), n=40, axis=1)),        # w_out > w_in
+    "real_out": (np.complex64, 32, np.float32, 17, lambda x: np.abs(np.fft.fft(x.astype(np.complex128), axis=1)[:, :17]) ** 2),  # 68-byte rows
+}
+
+
+class FakeIO:
+    """run(in_ptr, in2_ptr, out_ptr) of a numpy "plan": out = ref(x) (+ ref(x2)), stored row by row; `defect` names one fault."""
+
+    def __init__(self, shape, defect=None):
+        self.dt_in, self.w_in, self.dt_out, self.w_out, self.ref = IO_SHAPES[shape]
+        self.dt_in, self.dt_out = np.dtype(self.dt_in), np.dtype(self.dt_out)
+        self.defect, self.runs = defect, 0
+
+    def ref2(self, x, x2):
+        return self.ref(x) + self.ref(x2)
+
+    def __call__(self, in_ptr, in2_ptr, out_ptr):
+        mem = A.memory()
+        self.runs += 1
+        x = mem.d2h(in_ptr, (IO_BATCH, self.w_in), self.dt_in)
+        y = self.ref(x)
+        if in2_ptr is not None:
+            y = y + self.ref(mem.d2h(in2_ptr, (IO_BATCH, self.w_in), self.dt_in))
+        y = y.astype(self.dt_out)
+        d = self.defect
+        if d == "swap":
+            y[[2, 5]] = y[[5, 2]]
+        elif d == "neighbour_bin":
+            y[3, 11] = y[4, 11]
+        elif d == "tail_nan":
+            y[4, self.w_out - 1] = np.nan
+        rb = self.w_out * self.dt_out.itemsize
+        for b in range(IO_BATCH):  # the store order of a kernel that walks the rows
+            if d == "tail_unwritten" and b == 4:
+                mem.h2d(out_ptr + b * rb, y[b, :-1])
+                continue
+            mem.h2d(out_ptr + b * rb, y[b])
+            if d == "past_row":  # one element past the row: the next row's first element, which that row's own store then repairs
+                mem.h2d(out_ptr + (b + 1) * rb, y[b, :1])
+        if d == "guard":
+            mem.h2d(out_ptr + IO_BATCH * rb, np.zeros(1, np.uint32))  # the first word of the trailing guard
+        if d == "input2" and in2_ptr is not None:
+            mem.h2d(in2_ptr + 5 * self.w_in * self.dt_in.itemsize + 8, np.zeros(1, np.uint32))
+        if d == "inplace_differs" and in_ptr == out_ptr:
+            w = mem.d2h(out_ptr + 3 * rb, (1,), np.uint32)
+            mem.h2d(out_ptr + 3 * rb, w ^ np.uint32(1))
+
+
+def _io_check(shape, defect=None, second=True, inplace=False):
+    f = FakeIO(shape, defect)
+    x = A.normal_rows(f.w_in, 0, IO_BATCH, f.dt_in, seed=31)
+    x2 = A.normal_rows(f.w_in, 100, IO_BATCH, f.dt_in, seed=31) if second else None
+    e = A.check_execute_io(f, x, f.w_out, f.dt_out, "multipass", f.ref2 if second else f.ref, x2=x2, n=40, inplace=inplace,
+                           label="fake " + shape)
+    return f, e
+
+
+@pytest.mark.parametrize("shape", sorted(IO_SHAPES))
+def test_io_correct_execute_passes(host_memory, shape):
+    f, e = _io_check(shape, second=True)
+    assert e.shape == (IO_BATCH,) and np.all(np.isfinite(e)) and f.runs == 1
+    f, e = _io_check(shape, second=False, inplace=True)
+    assert f.runs == 2 and np.max(e) <= A.bound("multipass", f.dt_out, 40)
+
+
+def test_io_payload_is_aligned_like_a_plain_allocation(host_memory):
+    """68-byte rows: the guards are 80 bytes, the payload starts 16-byte aligned and the trailing guard right behind it."""
+    g = A.Guarded(5, 68, align16=True)
+    assert g.guard_bytes == 80 and g.ptr % 16 == 0 and g.ptr - g.base == 80
+    assert g.guards_intact()
+    A.h2d(g.ptr + 5 * 68, np.zeros(1, np.uint32))
+    assert not g.guards_intact()
+    g.free()
+    assert A.Guarded(5, 64).guard_bytes == 64 and A.Guarded(5, 8).guard_bytes == 8  # check_execute's buffers are as they were
+
+
+@pytest.mark.parametrize("shape", sorted(IO_SHAPES))
+@pytest.mark.parametrize("defect,match", [
+    ("past_row", "wrote outside"),  # every stray element but the last row's is overwritten by the next row: the guard sees the last
+    ("guard", "wrote outside"),
+    ("tail_nan", "worst transform 4 .*non-finite 1"),
+    ("tail_unwritten", "worst transform 4 .*non-finite 1"),
+    ("swap", "2 of 7 transforms over the bound.*\\[2, 5\\]"),
+    ("neighbour_bin", "1 of 7 transforms over the bound.*worst transform 3 \\(bin 11"),
+    ("input2", "changed its second input"),
+])
+def test_io_defects_flagged(host_memory, shape, defect, match):
+    with pytest.raises(AssertionError, match=match):
+        _io_check(shape, defect)
+    _io_check(shape, None)  # the same call without the defect passes
+
+
+def test_io_in_place_must_match_out_of_place(host_memory):
+    with pytest.raises(AssertionError, match="in-place result differs from the out-of-place one at row 3"):
+        _io_check("truncated", "inplace_differs", second=False, inplace=True)
+
+
+def test_row_errors_scaled_by_the_larger_of_rms_and_bin():
+    """scale="rms_or_bin": a peak's own rounding error is measured against the peak, every other bin against the row's RMS."""
+    rng = np.random.default_rng(4)
+    X = rng.standard_normal((3, 256))
+    X[:, 0] = 1000.0  # the lag 0 of a correlation
+    rms = np.sqrt(np.mean(X ** 2, axis=1))
+    y = X.copy()
+    y[1, 0] *= 1 + 1e-6  # a relative error of 1e-6 on the peak
+    e_old, k_old = A.row_errors(y, X)
+    e_new, k_new = A.row_errors(y, X, scale="rms_or_bin")
+    assert k_old[1] == 0 and np.isclose(e_old[1], 1e-3 / rms[1]) and np.isclose(e_new[1], 1e-6)
+    y = X.copy()
+    y[2, 77] += 1e-3  # the same absolute error on an ordinary bin: unchanged by the option, unless that bin is above the RMS
+    e_new, k_new = A.row_errors(y, X, scale="rms_or_bin")
+    assert k_new[2] == 77 and np.isclose(e_new[2], 1e-3 / max(rms[2], abs(X[2, 77])))
+    y[0, 5] = np.nan
+    assert np.isinf(A.row_errors(y, X, scale="rms_or_bin")[0][0])
+    with pytest.raises(ValueError):
+        A.row_errors(y, X, scale="max")

@@ -133,3 +133,99 @@ def test_chained_pass_over_several_launch_groups(kind, monkeypatch):
     assert info[1] == 2 and info[3] == 16, info  # chained, launch groups of 16
     ref = O.oracle_xcorr(x, y) if kind == "xcorr" else O.oracle_conv_circular(x, h)
     assert rel(out, ref) < TOL[np.dtype(np.complex128)] * 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# every row against float64 (tests/accuracy.py), outputs between sentinel rows (emu_lib.*_guarded), at the cases of
+# tests/ext_ladder.py: the same properties the GPU runs in tests/test_gpu_ext_every_row.py
+# ---------------------------------------------------------------------------------------------------------------------------
+import accuracy as A  # noqa: E402
+import ext_ladder as L  # noqa: E402
+
+
+def _same_bits(a, b, what):
+    assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)), what
+
+
+@pytest.mark.parametrize("rows,cols,nm,dtype,lds,path,why", L.EMU_2D, ids=lambda v: None if isinstance(v, str) else str(v))
+def test_fft2d_every_matrix_emulated(rows, cols, nm, dtype, lds, path, why):
+    x = L.complex_rows(rows * cols, nm, dtype, seed=rows + cols).reshape(nm, rows, cols)
+    for d in (-1, 1):
+        y, info = E.emu_fft2d_guarded(x, d, lds_budget=lds)
+        assert info[0] == path, (why, info[0])
+        A.check_rows(y.reshape(nm, -1), x.reshape(nm, -1), d, "2d", n=rows * cols, ref=L.ref_2d(rows, cols, d), label="emulated 2D: " + why)
+        z, _ = E.emu_fft2d_guarded(x, d, lds_budget=lds, inplace=True)
+        _same_bits(z, y, "2D in place differs from out of place: " + why)
+
+
+@pytest.mark.parametrize("dtype", [L.F32, L.F64], ids=str)
+@pytest.mark.parametrize("n,batch", L.EMU_REAL)
+def test_r2c_c2r_every_row_emulated(n, batch, dtype):
+    """r2c against rfft of the float64 input; c2r of r2c results and of random Hermitian half spectra (L.half_spectra says why
+    only those) against irfft; guards, untouched inputs, in place through one buffer of batch * (n/2 + 1) complex values."""
+    x = L.real_rows(n, batch, dtype, seed=n)
+    X = E.emu_r2c_guarded(x)
+    assert X.shape == (batch, n // 2 + 1)
+    A.check_rows(X, x, -1, "r2c", n=n, ref=L.ref_r2c, label="emulated r2c")
+    _same_bits(E.emu_r2c_guarded(x, inplace=True), X, "r2c in place differs")
+    for S in (X, L.half_spectra(n, batch, X.dtype, seed=n + 1)):
+        back = E.emu_c2r_guarded(S, n)
+        A.check_rows(back, S, 1, "c2r", n=n, ref=L.ref_c2r(n), label="emulated c2r")
+        _same_bits(E.emu_c2r_guarded(S, n, inplace=True), back, "c2r in place differs")
+
+
+def _fused_emulated(kind, nx, nh, batch, dtype, lds, fused, passes, why, monkeypatch, chunk=None):
+    x = L.complex_rows(nx, batch, dtype, seed=nx)
+    y = L.complex_rows(nx, batch, dtype, seed=nx + 1) if kind == "xcorr" else None
+    h = L.complex_rows(nh if kind == "conv" else nx, 1, dtype, seed=nh + 7)[0] if kind in ("conv", "circ") else None
+    w_out, dt_out = L.fused_out(kind, nx, nh, dtype)
+    ref = L.ref_fused(kind, nx, nh, h, fs=48000.0)
+    X = ref(x, y) if kind == "xcorr" else ref(x)  # computed once, shared by the variants
+    assert X.shape == (batch, w_out)
+    for no_fusion, no_chain in ((0, 0), (1, 0), (0, 1)):
+        if no_chain:
+            monkeypatch.setenv("FFT_EMU_NO_CHAIN", "1")
+        out, info = E.emu_fused_guarded(kind, x, y=y, h=h, lds_budget=lds, no_fusion=bool(no_fusion), fs=48000.0)
+        monkeypatch.delenv("FFT_EMU_NO_CHAIN", raising=False)
+        assert out.dtype == dt_out and out.shape == (batch, w_out)
+        assert info[0] == passes and info[1] == (0 if no_fusion else min(fused, 1) if no_chain else fused), (why, info)
+        if chunk:
+            assert info[3] == chunk, info
+        A.check_rows(out, X, 0, L.FUSED_FAMILY[kind], out.dtype, n=nx, m=L.fused_m(kind, nx, nh), ref=lambda Xs: Xs, scale="rms_or_bin",
+                     label="emulated %s (%s) no_fusion=%d no_chain=%d" % (kind, why, no_fusion, no_chain))
+
+
+@pytest.mark.parametrize("kind,nx,nh,batch,dtype,lds,fused,passes,why", L.EMU_FUSED, ids=lambda v: None if isinstance(v, str) and " " in v else str(v))
+def test_fused_every_row_emulated(kind, nx, nh, batch, dtype, lds, fused, passes, why, monkeypatch):
+    _fused_emulated(kind, nx, nh, batch, dtype, lds, fused, passes, why, monkeypatch)
+
+
+@pytest.mark.parametrize("kind,nx,dtype,chunk", [("xcorr", 1500, L.C128, 16), ("autocorr", 1500, L.C64, 32)], ids=str)
+def test_fused_every_row_over_launch_groups_emulated(kind, nx, dtype, chunk, monkeypatch):
+    """FFT_HIP_CHUNK_MB = 1: m = 4096 runs in launch groups of 16 (fp64) / 32 (fp32) transforms, 37 = 16 + 16 + 5 / 32 + 5; the
+    cross-correlation's per-transform table must follow the group offset in the chained kernel and in the two-kernel path."""
+    monkeypatch.setenv("FFT_HIP_CHUNK_MB", "1")
+    _fused_emulated(kind, nx, 0, 37, dtype, 40000, 2, 2, "launch groups", monkeypatch, chunk=chunk)
+
+
+@pytest.mark.parametrize("kind,nx,nh", [("conv", 101, 8), ("conv", 100, 18), ("conv", 127, 2), ("conv", 128, 1), ("autocorr", 33, 0), ("xcorr", 33, 0)])
+def test_budget_too_small_for_m_128_fp64_is_refused(kind, nx, nh):
+    """fp64, lds_budget = 4096, m = 128: the plan build fails, and that is the budget doing what it should, not a planner gap.
+    A multi-pass split needs both factors >= 16 (Pow2Plan::build: l1 = 4 ... log2n - 4), so n = 32, 64, 128 are single-pass
+    sizes by construction; the single-pass tile of 128 complex128 values (2 KiB) and its tables do not fit 4096 bytes, so no
+    schedule exists -- the plain 1D plan of n = 128 refuses the same budget.  The device plans with 160 KiB, where every such
+    size fits; one step more budget (8192) or one size up (m = 256 = 16 x 16) builds and passes."""
+    x = L.complex_rows(nx, 3, L.C128, seed=nx)
+    y = L.complex_rows(nx, 3, L.C128, seed=nx + 1) if kind == "xcorr" else None
+    h = L.complex_rows(nh, 1, L.C128, seed=3)[0] if kind == "conv" else None
+    assert L.fused_m(kind, nx, nh) == 128
+    with pytest.raises(RuntimeError, match="emu_fused failed"):
+        E.emu_fused(kind, x, y=y, h=h, lds_budget=4096)
+    with pytest.raises(RuntimeError, match="emu_fft failed"):
+        E.emu_fft(L.complex_rows(128, 3, L.C128, seed=1), lds_budget=4096)
+    out, info = E.emu_fused_guarded(kind, x, y=y, h=h, lds_budget=8192)
+    assert info[0] == 1
+    ref = L.ref_fused(kind, nx, nh, h)
+    A.check_rows(out, ref(x, y) if kind == "xcorr" else ref(x), 0, L.FUSED_FAMILY[kind], out.dtype, n=nx, m=128, ref=lambda Xs: Xs, scale="rms_or_bin")
+    out, info = E.emu_fused_guarded("autocorr", L.complex_rows(100, 3, L.C128, seed=2), lds_budget=4096)  # m = 256: two passes of 16
+    assert info[0] == 2 and info[2] == 8
