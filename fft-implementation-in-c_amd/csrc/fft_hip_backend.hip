@@ -777,10 +777,19 @@ static fft_gpu_plan_t finish_plan(fft_gpu_plan* p, bool ok, const char* what) {
     return p;
 }
 
+// FFT_GPU_ALGO_AUTO / FFT_GPU_ALGO_MIXED_RADIX of the 2D and real plans: does the plan put its 7-smooth lengths on the
+// mixed-radix engine?  -1: an algorithm these plans do not take
+static int smooth_of(fft_gpu_algo_t algo) {
+    if (algo == FFT_GPU_ALGO_MIXED_RADIX) return 1;
+    if (algo == FFT_GPU_ALGO_AUTO) return g_smooth_policy == 1 ? 1 : 0;
+    return -1;
+}
+
 // 2D complex transform of `n_matrices` row-major rows x cols matrices (replaces the stub gpu/fft_gpu.c:377-385)
-fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec) {
-    if (rows <= 0 || cols <= 0 || n_matrices <= 0 || (long long)rows * cols > (1ll << 30)) {
-        fprintf(stderr, "fft_hip: invalid 2D plan arguments (rows=%d cols=%d matrices=%d)\n", rows, cols, n_matrices);
+fft_gpu_plan_t fft_gpu_plan_2d_algo_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec, fft_gpu_algo_t algo) {
+    const int smooth = smooth_of(algo);
+    if (rows <= 0 || cols <= 0 || n_matrices <= 0 || (long long)rows * cols > (1ll << 30) || smooth < 0) {
+        fprintf(stderr, "fft_hip: invalid 2D plan arguments (rows=%d cols=%d matrices=%d algo=%d)\n", rows, cols, n_matrices, (int)algo);
         return NULL;
     }
     fft_gpu_plan* p = new_plan_shell(rows * cols, n_matrices, (int)dir, prec, PLAN_2D);
@@ -789,19 +798,23 @@ fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_di
     bool ok;
     if (prec == FFT_PREC_F32) {
         p->d32 = new (std::nothrow) ffteng::Plan2D<float, HipRT>();
-        ok = p->d32 && p->d32->build(&p->rt, rows, cols, p->dir, n_matrices);
+        ok = p->d32 && p->d32->build(&p->rt, rows, cols, p->dir, n_matrices, smooth == 1);
     } else {
         p->d64 = new (std::nothrow) ffteng::Plan2D<double, HipRT>();
-        ok = p->d64 && p->d64->build(&p->rt, rows, cols, p->dir, n_matrices);
+        ok = p->d64 && p->d64->build(&p->rt, rows, cols, p->dir, n_matrices, smooth == 1);
     }
     return finish_plan(p, ok, "2D");
+}
+fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec) {
+    return fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, dir, prec, FFT_GPU_ALGO_AUTO);
 }
 fft_gpu_plan_t fft_gpu_plan_2d_hip(int rows, int cols, fft_direction dir) { return fft_gpu_plan_2d_ex_hip(rows, cols, 1, dir, FFT_PREC_F64); }
 
 // real-input forward / real-output inverse 1D transforms, n/2 + 1 bins (reference stubs algorithms/auto/fft_auto.c:391-409)
-static fft_gpu_plan_t plan_real(int n, int batch, fft_precision_t prec, bool r2c) {
-    if (n <= 0 || batch <= 0) {
-        fprintf(stderr, "fft_hip: invalid real-transform plan arguments (n=%d batch=%d)\n", n, batch);
+static fft_gpu_plan_t plan_real(int n, int batch, fft_precision_t prec, bool r2c, fft_gpu_algo_t algo) {
+    const int smooth = smooth_of(algo);
+    if (n <= 0 || batch <= 0 || smooth < 0) {
+        fprintf(stderr, "fft_hip: invalid real-transform plan arguments (n=%d batch=%d algo=%d)\n", n, batch, (int)algo);
         return NULL;
     }
     fft_gpu_plan* p = new_plan_shell(n, batch, r2c ? -1 : 1, prec, r2c ? PLAN_R2C : PLAN_C2R);
@@ -809,15 +822,17 @@ static fft_gpu_plan_t plan_real(int n, int batch, fft_precision_t prec, bool r2c
     bool ok;
     if (prec == FFT_PREC_F32) {
         p->r32 = new (std::nothrow) ffteng::RealPlan<float, HipRT>();
-        ok = p->r32 && p->r32->build(&p->rt, n, r2c, batch);
+        ok = p->r32 && p->r32->build(&p->rt, n, r2c, batch, smooth == 1);
     } else {
         p->r64 = new (std::nothrow) ffteng::RealPlan<double, HipRT>();
-        ok = p->r64 && p->r64->build(&p->rt, n, r2c, batch);
+        ok = p->r64 && p->r64->build(&p->rt, n, r2c, batch, smooth == 1);
     }
     return finish_plan(p, ok, r2c ? "r2c" : "c2r");
 }
-fft_gpu_plan_t fft_gpu_plan_r2c_1d_hip(int n, int batch, fft_precision_t prec) { return plan_real(n, batch, prec, true); }
-fft_gpu_plan_t fft_gpu_plan_c2r_1d_hip(int n, int batch, fft_precision_t prec) { return plan_real(n, batch, prec, false); }
+fft_gpu_plan_t fft_gpu_plan_r2c_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo) { return plan_real(n, batch, prec, true, algo); }
+fft_gpu_plan_t fft_gpu_plan_c2r_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo) { return plan_real(n, batch, prec, false, algo); }
+fft_gpu_plan_t fft_gpu_plan_r2c_1d_hip(int n, int batch, fft_precision_t prec) { return plan_real(n, batch, prec, true, FFT_GPU_ALGO_AUTO); }
+fft_gpu_plan_t fft_gpu_plan_c2r_1d_hip(int n, int batch, fft_precision_t prec) { return plan_real(n, batch, prec, false, FFT_GPU_ALGO_AUTO); }
 
 // fused consumers (fft_plans_ext.h FusedPlan); h_host: the nh kernel samples of a convolution (host memory, element
 // type of `prec`), ignored otherwise
@@ -1245,6 +1260,7 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);
+        if (a->mr) fill_mixed(a->mr);
         if (a->bl) {
             fill(&a->bl->core);
             info->bluestein_m = 1 << a->bl->log2m;
@@ -1262,6 +1278,7 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (d->colp)
             for (size_t i = 0; i < d->colp->passes.size() && i < 4; i++) info->factors[i] = 1 << d->colp->passes[i].log2L;
         if (d->tbuf) info->workspace_bytes += (size_t)d->rows * (size_t)d->cols * (size_t)d->max_matrices * sizeof(*d->tbuf);
+        if (d->colt && d->colt->mr) info->workspace_bytes += d->colt->mr->scratch_bytes;  // (a two-pass mixed-radix plan on the transposed image)
     };
     if (p->d32) fill_2d(p->d32);
     if (p->d64) fill_2d(p->d64);

@@ -10,7 +10,9 @@
 namespace ffteng {
 
 // ---------------------------------------------------------------------------
-// Batched complex 1D transform of ANY length with a fixed direction: the power-of-two engine or Bluestein.
+// Batched complex 1D transform of ANY length with a fixed direction: the power-of-two engine or Bluestein -- or, where the
+// caller asks for it (smooth), the mixed-radix plan for a 7-smooth length that is no power of two (what
+// fft_gpu_plan_1d_ex_hip does with FFT_GPU_ALGO_MIXED_RADIX: a device whose LDS holds no such schedule gets chirp-z).
 // ---------------------------------------------------------------------------
 template <typename T, typename RT>
 class AnyPlan {
@@ -18,8 +20,9 @@ class AnyPlan {
     int n = 0, dir = -1;
     Pow2Plan<T, RT>* p2 = nullptr;
     BluesteinPlan<T, RT>* bl = nullptr;
-    ~AnyPlan() { delete p2; delete bl; }
-    bool build(RT* rt, int n_, int dir_, int batch, int algo = ALGO_AUTO) {
+    MixedRadixPlan<T, RT>* mr = nullptr;
+    ~AnyPlan() { delete p2; delete bl; delete mr; }
+    bool build(RT* rt, int n_, int dir_, int batch, int algo = ALGO_AUTO, bool smooth = false) {
         n = n_;
         dir = dir_ < 0 ? -1 : 1;
         if (n >= 1 && (n & (n - 1)) == 0) {
@@ -27,11 +30,18 @@ class AnyPlan {
             return p2->build(rt, ilog2(n), algo, batch);
         }
         if (n < 1 || n > (1 << 29)) return false;
+        if (smooth && mr_passes(n) > 0) {
+            mr = new MixedRadixPlan<T, RT>();
+            if (mr->build(rt, n, batch)) return true;
+            delete mr;
+            mr = nullptr;
+        }
         bl = new BluesteinPlan<T, RT>();
         return bl->build(rt, n, dir, algo, batch);
     }
     void execute(const cpx<T>* in, cpx<T>* out, int nb) {
         if (p2) p2->execute(in, out, nb, dir > 0);
+        else if (mr) mr->execute(in, out, nb, dir > 0);
         else if (bl) bl->execute(in, out, nb);
     }
 };
@@ -51,6 +61,9 @@ static void launch_flat(RT* rt, K kernel, long long total, A... args) {
 //   columns = a strided batch: the column pass of the four-step engine in place (rows a power of two that fits one
 //             LDS tile with >= 64-byte row segments, cols a multiple of the 16-byte lane access), the same transforms as two
 //             strided passes with wide tiles for more rows, otherwise transpose -> batched 1D -> transpose.
+// smooth (FFT_GPU_ALGO_MIXED_RADIX, or AUTO under the smooth policy): 7-smooth lengths that are no power of two run on the
+// mixed-radix engine, each dimension decided on its own -- the rows through AnyPlan, the columns of a row count that is no
+// power of two through AnyPlan on the transposed image (power-of-two row counts keep their strided column passes).
 // The inverse is scaled ONCE by 1 / (rows * cols): each 1D inverse carries its own 1 / length and nothing is applied on
 // top (the reference's image_fft.c:64-71 divides by rows * cols AGAIN after two already scaled 1D inverses).
 // ---------------------------------------------------------------------------
@@ -70,11 +83,11 @@ class Plan2D {
         delete colt;
         if (rt && tbuf) rt->dfree(tbuf);
     }
-    bool build(RT* runtime, int rows_, int cols_, int dir_, int n_matrices) {
+    bool build(RT* runtime, int rows_, int cols_, int dir_, int n_matrices, bool smooth = false) {
         rt = runtime; rows = rows_; cols = cols_; dir = dir_ < 0 ? -1 : 1; max_matrices = n_matrices;
         if (rows < 1 || cols < 1 || n_matrices < 1 || (long long)rows * cols > (1ll << 30) ||
             (long long)rows * n_matrices > 0x7fffffff || (long long)cols * n_matrices > 0x7fffffff) return false;
-        if (!rowp.build(rt, cols, dir, rows * n_matrices)) return false;
+        if (!rowp.build(rt, cols, dir, rows * n_matrices, ALGO_AUTO, smooth)) return false;
         if (rows > 1) {
             if ((rows & (rows - 1)) == 0) {
                 colp = new Pow2Plan<T, RT>();
@@ -95,7 +108,7 @@ class Plan2D {
             }
             if (!colp) {
                 colt = new AnyPlan<T, RT>();
-                if (!colt->build(rt, rows, dir, cols * n_matrices)) return false;
+                if (!colt->build(rt, rows, dir, cols * n_matrices, ALGO_AUTO, smooth)) return false;
                 tbuf = (cpx<T>*)rt->dmalloc((size_t)rows * cols * n_matrices * SZ);
                 if (!tbuf) return false;
             }
@@ -123,7 +136,8 @@ class Plan2D {
 // its r2c "implementation" copies into a temporary, plans on it and frees it -- a use-after-free, fft_auto.c:391-402 --
 // and c2r returns NULL).  Even n: ONE complex transform of length n/2 on the real array read as complex, plus a split /
 // merge kernel (fft_kernels_ext.h); odd n: promoted to a complex transform of length n.  c2r is scaled by 1/n like every
-// inverse of the library, so c2r(r2c(x)) = x.
+// inverse of the library, so c2r(r2c(x)) = x.  smooth: a 7-smooth half length (odd n: length) that is no power of two runs on
+// the mixed-radix engine; the split / merge / promote / extend kernels are the same.
 // ---------------------------------------------------------------------------
 template <typename T, typename RT>
 class RealPlan {
@@ -141,11 +155,11 @@ class RealPlan {
         if (rt && work) rt->dfree(work);
     }
     bool even() const { return (n & 1) == 0; }
-    bool build(RT* runtime, int n_, bool r2c, int batch) {
+    bool build(RT* runtime, int n_, bool r2c, int batch, bool smooth = false) {
         rt = runtime; n = n_; forward = r2c; max_batch = batch; h = n / 2;
         if (n < 1 || batch < 1) return false;
         if (even()) {
-            if (!core.build(rt, h, r2c ? -1 : 1, batch)) return false;
+            if (!core.build(rt, h, r2c ? -1 : 1, batch, ALGO_AUTO, smooth)) return false;
             std::vector<cpx<T>> t;
             make_twiddle_table<T>(t, n, (long long)h + 1, 1);
             w = (cpx<T>*)rt->dmalloc(t.size() * SZ);
@@ -153,7 +167,7 @@ class RealPlan {
             if (!w || !work) return false;
             rt->h2d(w, t.data(), t.size() * SZ);
         } else {
-            if (!core.build(rt, n, r2c ? -1 : 1, batch)) return false;
+            if (!core.build(rt, n, r2c ? -1 : 1, batch, ALGO_AUTO, smooth)) return false;
             work = (cpx<T>*)rt->dmalloc((size_t)batch * (size_t)n * SZ);
             if (!work) return false;
         }

@@ -62,6 +62,8 @@ SIGNATURES = {
     "fft_gpu_mixed_radix_passes_hip": (_i, [_i]), "fft_gpu_set_smooth_policy_hip": (_i, [_i]),
     "fft_gpu_plan_2d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_2d_ex_hip": (_vp, [_i, _i, _i, _i, _i]),
     "fft_gpu_plan_r2c_1d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_c2r_1d_hip": (_vp, [_i, _i, _i]),
+    "fft_gpu_plan_2d_algo_hip": (_vp, [_i, _i, _i, _i, _i, _i]),
+    "fft_gpu_plan_r2c_1d_algo_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_1d_algo_hip": (_vp, [_i, _i, _i, _i]),
     "fft_gpu_plan_fused_hip": (_vp, [_i, _i, _i, _vp, _i, _i]), "fft_gpu_fused_out_len_hip": (_i, [_vp]),
     "fft_gpu_execute_fused_hip": (_i, [_vp, _vp, _vp, _vp, C.c_double]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
@@ -77,7 +79,8 @@ SIGNATURES = {
     "fft_gpu_device_count": (_i, []), "fft_gpu_alloc_f32": (_vp, [_sz]),
     "fft_gpu_copy_h2d_f32": (None, [_vp, _vp, _sz]), "fft_gpu_copy_d2h_f32": (None, [_vp, _vp, _sz]),
     "fft_gpu_memory_ptr": (_vp, [_vp]), "fft_gpu_plan_1d_f32": (_vp, [_i, _i, _i]),
-    "fft_gpu_plan_1d_ex": (_vp, [_i, _i, _i, _i, _i]), "fft_gpu_plan_info": (_i, [_vp, C.POINTER(PlanInfo)]),
+    "fft_gpu_plan_1d_ex": (_vp, [_i, _i, _i, _i, _i]), "fft_gpu_plan_2d_algo": (_vp, [_i, _i, _i, _i, _i, _i]),
+    "fft_gpu_plan_info": (_i, [_vp, C.POINTER(PlanInfo)]),
     "fft_gpu_plan_set_stream": (_i, [_vp, _vp]), "fft_gpu_execute_async": (_i, [_vp, _vp, _vp]),
     "fft_gpu_execute_ptr": (_i, [_vp, _vp, _vp]), "fft_gpu_plan_sync": (_i, [_vp]),
     "fft_gpu_execute_timed": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_float)]),
@@ -276,16 +279,17 @@ class ExtPlan:
         self.handle = handle
 
     @classmethod
-    def fft2d(cls, rows, cols, n_matrices=1, direction=FFT_FORWARD, dtype=np.complex128):
-        return cls(init().fft_gpu_plan_2d_ex_hip(rows, cols, n_matrices, direction, _prec_of(np.dtype(dtype))))
+    def fft2d(cls, rows, cols, n_matrices=1, direction=FFT_FORWARD, dtype=np.complex128, algo=ALGO_AUTO):
+        """algo (here and in r2c / c2r): ALGO_AUTO or ALGO_MIXED_RADIX (7-smooth lengths on the mixed-radix engine)."""
+        return cls(init().fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, direction, _prec_of(np.dtype(dtype)), algo))
 
     @classmethod
-    def r2c(cls, n, batch=1, dtype=np.float64):
-        return cls(init().fft_gpu_plan_r2c_1d_hip(n, batch, PREC_F32 if np.dtype(dtype) == np.float32 else PREC_F64))
+    def r2c(cls, n, batch=1, dtype=np.float64, algo=ALGO_AUTO):
+        return cls(init().fft_gpu_plan_r2c_1d_algo_hip(n, batch, PREC_F32 if np.dtype(dtype) == np.float32 else PREC_F64, algo))
 
     @classmethod
-    def c2r(cls, n, batch=1, dtype=np.float64):
-        return cls(init().fft_gpu_plan_c2r_1d_hip(n, batch, PREC_F32 if np.dtype(dtype) == np.float32 else PREC_F64))
+    def c2r(cls, n, batch=1, dtype=np.float64, algo=ALGO_AUTO):
+        return cls(init().fft_gpu_plan_c2r_1d_algo_hip(n, batch, PREC_F32 if np.dtype(dtype) == np.float32 else PREC_F64, algo))
 
     @classmethod
     def fused(cls, kind, nx, batch=1, h=None, dtype=np.complex128):
@@ -356,32 +360,32 @@ def _roundtrip(plan, x, out_shape, out_dtype, y=None, fused=False, fs=1.0):
     return res
 
 
-def fft2d(x, direction=FFT_FORWARD):
+def fft2d(x, direction=FFT_FORWARD, algo=ALGO_AUTO):
     """x: [rows, cols] or [matrices, rows, cols] complex -> 2D transform of every matrix."""
     x = np.ascontiguousarray(x)
     x3 = x.reshape((-1,) + x.shape[-2:])
-    plan = ExtPlan.fft2d(x3.shape[1], x3.shape[2], x3.shape[0], direction, x3.dtype)
+    plan = ExtPlan.fft2d(x3.shape[1], x3.shape[2], x3.shape[0], direction, x3.dtype, algo)
     y = _roundtrip(plan, x3, x3.shape, x3.dtype)
     plan.destroy()
     return y.reshape(x.shape)
 
 
-def rfft(x):
+def rfft(x, algo=ALGO_AUTO):
     """x: [batch, n] float32/float64 -> [batch, n//2 + 1] complex."""
     x = np.ascontiguousarray(x)
     batch, n = x.shape
     cdt = np.complex64 if x.dtype == np.float32 else np.complex128
-    plan = ExtPlan.r2c(n, batch, x.dtype)
+    plan = ExtPlan.r2c(n, batch, x.dtype, algo)
     y = _roundtrip(plan, x, (batch, n // 2 + 1), cdt)
     plan.destroy()
     return y
 
 
-def irfft(X, n):
+def irfft(X, n, algo=ALGO_AUTO):
     """X: [batch, n//2 + 1] complex -> [batch, n] real, scaled by 1/n."""
     X = np.ascontiguousarray(X)
     rdt = np.float32 if X.dtype == np.complex64 else np.float64
-    plan = ExtPlan.c2r(n, X.shape[0], rdt)
+    plan = ExtPlan.c2r(n, X.shape[0], rdt, algo)
     y = _roundtrip(plan, X, (X.shape[0], n), rdt)
     plan.destroy()
     return y

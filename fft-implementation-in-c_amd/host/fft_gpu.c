@@ -197,7 +197,12 @@ fft_gpu_plan_t fft_gpu_plan_2d(int rows, int cols, fft_direction direction) {
     return fft_gpu_plan_2d_hip(rows, cols, direction);
 }
 
-/* host arrays, row-major; one matrix */
+fft_gpu_plan_t fft_gpu_plan_2d_algo(int rows, int cols, int n_matrices, fft_direction direction, fft_precision_t prec, fft_gpu_algo_t algo) {
+    if (!backend_is_hip("fft_gpu_plan_2d_algo")) return NULL;
+    return fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, direction, prec, algo);
+}
+
+/* host arrays, row-major; one matrix (7-smooth sizes follow fft_gpu_set_smooth_policy_hip, like every AUTO plan) */
 int fft_gpu_dft_2d(complex_t* in, complex_t* out, int rows, int cols, fft_direction direction) {
     if (!in || !out || rows <= 0 || cols <= 0 || lazy_init() != 0) return -1;
     const size_t n = (size_t)rows * (size_t)cols;

@@ -96,10 +96,14 @@ typedef struct {
     int team_kernel;    /* which one-round-trip kernel team_tiles refers to: 0 none, 1 team_fft_kernel (csrc/fft_team.h), 2
                            team_defer_kernel (csrc/fft_team_defer.h), 3 team_quad_kernel (csrc/fft_team_quad.h: whole-line row
                            segments, both steps decimated by 4, the exchange in four rounds through the XCD's L2) */
-    /* r2c / c2r plans: algo ... team_kernel describe the complex core (length n/2 for even n, n for odd n).
-       2D plans: algo, chunk_batch, bluestein_m, team_* describe the row transforms (length cols); n_passes and factors the
-       strided column passes: 1 the direct column pass, 2 two strided passes, 0 the columns run on the transposed image
-       (or rows == 1: there are none). */
+    /* r2c / c2r plans: algo ... team_kernel describe the complex core (length n/2 for even n, n for odd n); a core on the
+       mixed-radix engine reports what the 1D mixed-radix plan of that length reports: algo = 7, bluestein_m = 0, n_passes
+       1 or 2, factors its split; fused = 0 (the split / merge runs as a kernel of its own).
+       2D plans: algo, chunk_batch, bluestein_m, team_* describe the row transforms (length cols): algo = 7 and
+       bluestein_m = 0 when they run on the mixed-radix engine; n_passes and factors the strided column passes: 1 the
+       direct column pass, 2 two strided passes, 0 the columns run on the transposed image -- every row count that is no
+       power of two, on the mixed-radix engine where it is 7-smooth and the plan asks for it -- (or rows == 1: there are none).
+       workspace_bytes includes the scratch images of two-pass mixed-radix cores. */
 } fft_gpu_plan_info_t;
 
 /* Per-plan switches (tests and integrators; nothing here changes results) */
@@ -161,6 +165,16 @@ fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_di
  * [batch][n] reals and writes [batch][n/2 + 1] complex bins; c2r the reverse, scaled by 1/n.  Execute with fft_gpu_execute_ptr. */
 fft_gpu_plan_t fft_gpu_plan_r2c_1d_hip(int n, int batch, fft_precision_t prec);
 fft_gpu_plan_t fft_gpu_plan_c2r_1d_hip(int n, int batch, fft_precision_t prec);
+/* The same three with the algorithm named.  algo: FFT_GPU_ALGO_AUTO (what the entry points above pass: 7-smooth lengths
+ * stay on chirp-z unless fft_gpu_set_smooth_policy_hip(1) is in force) or FFT_GPU_ALGO_MIXED_RADIX: every length of the
+ * plan with fft_gpu_mixed_radix_passes_hip(length) > 0 that is no power of two runs on the mixed-radix engine; anything
+ * else returns NULL.  2D decides rows and columns independently: 64 x 1000 keeps the power-of-two column pass and gets
+ * mixed-radix rows, 1009 x 1000 keeps chirp-z columns on the transposed image; 7-smooth row counts run on the transposed
+ * image with a mixed-radix plan (two passes above 4096 rows).  Real plans: the half-length (odd n: full-length) complex core; powers of two and other lengths get
+ * the plan AUTO builds. */
+fft_gpu_plan_t fft_gpu_plan_2d_algo_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec, fft_gpu_algo_t algo);
+fft_gpu_plan_t fft_gpu_plan_r2c_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo);
+fft_gpu_plan_t fft_gpu_plan_c2r_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo);
 /* fused consumers; h_host: the nh kernel samples (host memory, complex of `prec`) of the two convolutions, else ignored */
 fft_gpu_plan_t fft_gpu_plan_fused_hip(fft_gpu_fused_t kind, int nx, int nh, const void* h_host, int batch, fft_precision_t prec);
 int fft_gpu_fused_out_len_hip(fft_gpu_plan_t plan); /* elements per output row (complex; FFT_GPU_FUSED_PSD: real) */
@@ -194,7 +208,8 @@ int fft_gpu_set_policy_hip(int team_mode, int team_min_batch, int chunk_mb);
 /* what FFT_GPU_ALGO_MIXED_RADIX does with n: 0 not a mixed-radix length (not 7-smooth, above 2^23, n <= 0), 1 a single pass,
  * 2 two passes.  Host arithmetic only: works without a device. */
 int fft_gpu_mixed_radix_passes_hip(int n);
-/* which plan FFT_GPU_ALGO_AUTO builds for a non-power-of-two n, for plans created after the call: 0 (default) chirp-z, 1 the
+/* which plan FFT_GPU_ALGO_AUTO builds for a non-power-of-two n (1D plans, and the rows, columns and cores of 2D, r2c and c2r
+ * plans), for plans created after the call: 0 (default) chirp-z, 1 the
  * mixed-radix plan wherever fft_gpu_mixed_radix_passes_hip(n) > 0.  A negative argument changes nothing; returns the mode in
  * force.  fft_gpu_init seeds it once from FFT_HIP_SMOOTH. */
 int fft_gpu_set_smooth_policy_hip(int mode);
@@ -223,6 +238,7 @@ void fft_gpu_copy_d2h_f32(complex32_t* dst, fft_gpu_memory_t src, size_t n);
 void* fft_gpu_memory_ptr(fft_gpu_memory_t mem);
 fft_gpu_plan_t fft_gpu_plan_1d_f32(int n, int batch, fft_direction direction);
 fft_gpu_plan_t fft_gpu_plan_1d_ex(int n, int batch, fft_direction direction, fft_precision_t prec, fft_gpu_algo_t algo);
+fft_gpu_plan_t fft_gpu_plan_2d_algo(int rows, int cols, int n_matrices, fft_direction direction, fft_precision_t prec, fft_gpu_algo_t algo);
 int fft_gpu_plan_info(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 int fft_gpu_plan_set_stream(fft_gpu_plan_t plan, void* hip_stream);
 int fft_gpu_execute_async(fft_gpu_plan_t plan, fft_gpu_memory_t in, fft_gpu_memory_t out);
