@@ -90,6 +90,13 @@ struct ExecHooks {
     // single-pass plans only (execute_round): the spectral product between the forward and the inverse transform of ONE kernel
     const fftk::cpx<T>* mid_tab = nullptr;
     int mid_mode = fftk::HOOK_NONE;
+    // single-pass plans only (execute_frames): the transforms of the execute are overlapping FRAMES of signals, frame f at
+    // in + (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_pitch (in_pitch = the hop); 0: plain rows.
+    // power_out: not NULL = the store side writes one-sided power rows of n/2 + 1 reals there, scaled by power_scale.
+    int frames_per_signal = 0;
+    long long signal_pitch = 0;
+    T* power_out = nullptr;
+    T power_scale = (T)1;
 };
 
 enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6, ALGO_MIXED_RADIX = 7 };
@@ -1274,8 +1281,29 @@ class Pow2Plan {
             if (hook_kind(p) == 1) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 8>, tp, -1, p);
             return;
         }
+        if (h.frames_per_signal > 0) {  // overlapping frames (execute_frames): the hooked single-pass rows kernel with its framed load
+            if (hook_kind(p) != 1 || side != 3) return;
+            const long long hop = h.in_pitch ? h.in_pitch : n;
+            k.frames_per_signal = h.frames_per_signal;
+            k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
+            k.signal_pitch = h.signal_pitch;
+            // 16-byte loads only where EVERY frame starts 16-byte aligned: the base, the hop and the signal pitch
+            k.in_vec_ok = ((hop % V) == 0 && (h.signal_pitch % V) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+            if (((uintptr_t)out & 15) != 0) k.out_vec_ok = 0;
+            // a sample belongs to n / hop frames: the loads of overlapping frames carry no non-temporal hint (their lines are asked for again)
+            if (hop < n) tp.nt &= ~1;
+            if (h.power_out) {
+                k.power_out = h.power_out;
+                k.power_scale = h.power_scale;
+                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 32>, tp, -1, p);
+            } else {
+                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16>, tp, -1, p);
+            }
+            return;
+        }
         switch (hook_kind(p)) {
-            // HOOK bits: 1 load side, 2 store side, 4 table values prefetched with the data, 8 round trip (fft_kernels.h)
+            // HOOK bits: 1 load side, 2 store side, 4 table values prefetched with the data, 8 round trip, 16 framed load, 32 one-sided
+            // power store (fft_kernels.h)
             case 1: launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3>, tp, -1, p); break;
             case 2: launch_kernel(tile_fft_kernel<T, 8, 1, FAM_R4, LOAD_CCONTIG, STORE_CCONTIG, true, 0, 1 | 4>, tp, -1, p); break;
             case 3: launch_hooked_fixed<FAM_SR16, LOAD_LCONTIG, STORE_CCONTIG, false, 2>(tp, p); break;
@@ -1293,6 +1321,23 @@ class Pow2Plan {
         const T scale = (T)((1.0L / (long double)n) * (long double)extra_scale);
         run_if = nullptr;
         launch_pass_hooked(0, in, out, nb, false, scale, h, 3 | 4, 0);
+        rt->mark(0);
+    }
+
+    // ---- single-pass sizes: the nf transforms of one launch are overlapping frames of signals (ExecHooks::frames_per_signal,
+    // signal_pitch; in_pitch = the hop), windowed by h.pre_tab on the way in; the results leave as complex rows of n bins (out) or,
+    // with h.power_out, as one-sided power rows.  Requires round_capable() and frames_exact(nf, frames_per_signal).
+    // The frame -> (signal, frame in signal) split in the kernel is one multiply-high by ceil(2^32 / d): exact while f * d < 2^32
+    // for every tile column f, the padding columns of the last tile included.
+    bool frames_exact(long long nf, int frames_per_signal) const {
+        if (passes.empty() || nf < 1 || nf > 0x7fffffff) return false;
+        const long long C = 1ll << passes[0].log2C;
+        const long long cols = (nf + C - 1) / C * C;
+        return cols * (long long)frames_per_signal <= (1ll << 32);
+    }
+    void execute_frames(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
+        run_if = nullptr;
+        launch_pass_hooked(0, in, out, nf, false, (T)1, h, 3, 0);
         rt->mark(0);
     }
 

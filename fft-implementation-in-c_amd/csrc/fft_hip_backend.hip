@@ -307,7 +307,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -315,9 +315,11 @@ struct fft_gpu_plan {
     ffteng::RealPlan<double, HipRT>* r64 = nullptr;
     ffteng::FusedPlan<float, HipRT>* f32 = nullptr;
     ffteng::FusedPlan<double, HipRT>* f64 = nullptr;
+    ffteng::FramesPlan<float, HipRT>* w32 = nullptr;  // STFT / spectrogram / Welch on overlapping frames
+    ffteng::FramesPlan<double, HipRT>* w64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5 };
 
 namespace {
 
@@ -419,6 +421,8 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
     if (p->r64) any(&p->r64->core);
     if (p->f32) f(&p->f32->core);
     if (p->f64) f(&p->f64->core);
+    if (p->w32) f(&p->w32->core);
+    if (p->w64) f(&p->w64->core);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -471,6 +475,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->r32) p->r32->execute_c2r((const fftk::cpx<float>*)d_in, (float*)d_out, p->batch);
     else if (p->r64) p->r64->execute_c2r((const fftk::cpx<double>*)d_in, (double*)d_out, p->batch);
     else if (p->f32 || p->f64) return -1;  // fused consumers take two inputs: fft_gpu_execute_fused_hip
+    else if (p->w32 || p->w64) return -1;  // frames plans take a signal pitch and a sample rate: fft_gpu_execute_frames_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -731,6 +736,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->r64;
         delete p->f32;
         delete p->f64;
+        delete p->w32;
+        delete p->w64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -871,6 +878,52 @@ int fft_gpu_execute_fused_hip(fft_gpu_plan_t p, const void* d_x, const void* d_y
         if (p->f64->kind == ffteng::FUSED_XCORR && !d_y) return -1;
         p->f64->execute((const fftk::cpx<double>*)d_x, (const fftk::cpx<double>*)d_y, d_out, p->batch, sample_rate);
     }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+// STFT / spectrogram / Welch PSD on overlapping frames (fft_plans_ext.h FramesPlan); w_host: the n window values of
+// FFT_GPU_WINDOW_USER (host memory, reals of `prec`), ignored otherwise
+fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                       fft_gpu_frames_out_t out, fft_precision_t prec) {
+    if (n < 2 || (n & (n - 1)) != 0 || hop < 1 || hop > n || signal_len < n || n_signals < 1 || (int)window < 0 || (int)window > 4 ||
+        (window == FFT_GPU_WINDOW_USER && !w_host) || (int)out < 0 || (int)out > 2 ||
+        (long long)n_signals * ((signal_len - (n - hop)) / hop) > 0x7fffffff) {
+        fprintf(stderr, "fft_hip: invalid frames plan arguments (n=%d hop=%d signal_len=%d signals=%d window=%d out=%d)\n", n, hop, signal_len,
+                n_signals, (int)window, (int)out);
+        return NULL;
+    }
+    const int nw = (signal_len - (n - hop)) / hop;
+    fft_gpu_plan* p = new_plan_shell(n, n_signals * nw, -1, prec, PLAN_FRAMES);
+    if (!p) return NULL;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->w32 = new (std::nothrow) ffteng::FramesPlan<float, HipRT>();
+        ok = p->w32 && p->w32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out);
+    } else {
+        p->w64 = new (std::nothrow) ffteng::FramesPlan<double, HipRT>();
+        ok = p->w64 && p->w64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out);
+    }
+    return finish_plan(p, ok, "frames");
+}
+// frames per signal: nw = (signal_len - (n - hop)) / hop
+int fft_gpu_frames_count_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->w32) return p->w32->nw;
+    if (p->w64) return p->w64->nw;
+    return -1;
+}
+// async on the plan's stream.  d_x: the signals, signal_pitch elements apart (0: signal_len); d_out: see fft_gpu_frames_out_t
+int fft_gpu_execute_frames_hip(fft_gpu_plan_t p, const void* d_x, long long signal_pitch, void* d_out, double sample_rate) {
+    if (!p || !d_x || !d_out || d_x == d_out || (!p->w32 && !p->w64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->w32 ? p->w32->execute((const fftk::cpx<float>*)d_x, signal_pitch, d_out, sample_rate)
+                          : p->w64->execute((const fftk::cpx<double>*)d_x, signal_pitch, d_out, sample_rate);
+    if (rc != 0) return -1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
@@ -1117,7 +1170,9 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->b64) p->b64->no_fusion = value != 0;
             if (p->f32) p->f32->no_fusion = value != 0;
             if (p->f64) p->f64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64) ? 0 : -1;
+            if (p->w32) p->w32->no_fusion = value != 0;
+            if (p->w64) p->w64->no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
@@ -1257,6 +1312,14 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->f32) fill_fused(p->f32);
     if (p->f64) fill_fused(p->f64);
+    auto fill_frames = [&](auto* w) {  // n, batch = signals * frames, the core's passes; fused: framed load and stores ride on the pass
+        fill(&w->core);
+        info->fused = w->fused() ? 1 : 0;
+        if (w->power) info->workspace_bytes += (size_t)w->frames() * (size_t)w->bins() * sizeof(*w->power);
+        if (w->work) info->workspace_bytes += (size_t)w->frames() * (size_t)w->n * sizeof(*w->work);
+    };
+    if (p->w32) fill_frames(p->w32);
+    if (p->w64) fill_frames(p->w64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

@@ -84,6 +84,18 @@ struct TileHooks {
     // goes through the store side above (post_tab / n_out), scaled by TileParams::scale.
     const cpx<T>* mid_tab;
     int mid_mode;
+    // HOOK bit 4 (single-pass kernel only): FRAMED load.  Tile column t is frame f = c0 + t of the execute, and its samples start at
+    // in + (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_c: overlapping frames (in_c = the hop) of
+    // many signals.  frames_rcp = ceil(2^32 / frames_per_signal): the quotient is one multiply-high, exact for every f the
+    // launcher lets through (f * frames_per_signal < 2^32); unused when frames_per_signal == 1.
+    int frames_per_signal;
+    unsigned frames_rcp;
+    long long signal_pitch;
+    // HOOK bit 5 (single-pass kernel only): ONE-SIDED POWER store.  Instead of complex bins the store side writes reals,
+    // power_out[f * (L/2 + 1) + k] = |X[k]|^2 * power_scale, doubled for 0 < k < L/2, k <= L/2 only (reference
+    // applications/power_spectrum.c:75-80).  Rows of L/2 + 1 values start only sizeof(T)-aligned: scalar stores.
+    T* power_out;
+    T power_scale;
 };
 
 template <typename T>
@@ -469,7 +481,9 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 // stage loop unrolls (fewer address VGPRs, less integer VALU); FIXED == 0 reads both from the parameters.
 // HOOK: 0 none; bit 0 the load side of TileHooks is compiled in, bit 1 the store side, bit 2 the load-side table values
 // are prefetched together with the data (+ E * 4 VGPRs per group: the 2-waves-per-SIMD kernels; without it they are read
-// when the data is consumed -- the 4-waves-per-SIMD rows kernel, whose 128-VGPR budget has no room for them)
+// when the data is consumed -- the 4-waves-per-SIMD rows kernel, whose 128-VGPR budget has no room for them), bit 3 FFT ->
+// product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store (TileHooks; the last three on the
+// hooked single-pass rows kernel only).  Compile-time bits: an instantiation without one compiles to the code it had before.
 // waves per SIMD the register budget of an instantiation is sized for.  The fp32 kernels with their shape baked in need only
 // 92-122 VGPRs when built for four waves per SIMD (no spills; built for two they take 150-250 because they may), i.e. two
 // 512-thread workgroups per CU.  Measured (profiles/r2_ab_rows_fixed.txt): the single-pass rows kernel gains 5...12 % from
@@ -541,6 +555,9 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
     constexpr int DEPTH = FFT_DEPTH;  // 2 = double-buffered prefetch (+32 VGPRs; needs FFT_FORCE_OPAQUE to stay spill-free)
     vec16<T> nxtbuf[DEPTH][H][E];
     constexpr bool HK_LOAD = (HOOK & 1) != 0, HK_STORE = (HOOK & 2) != 0, HK_TABPF = (HOOK & 4) != 0, HK_ROUND = (HOOK & 8) != 0;
+    constexpr bool HK_FRAMES = (HOOK & 16) != 0, HK_POWER = (HOOK & 32) != 0;  // TileHooks: framed load, one-sided power store
+    static_assert(!(HK_FRAMES || HK_POWER) || (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && HK_LOAD && HK_STORE),
+                  "frames / power hooks: the hooked single-pass rows kernel only");
     vec16<T> nxttab[HK_TABPF ? DEPTH : 1][HK_TABPF ? H : 1][HK_TABPF ? E : 1];  // the load-side table values of the same chunks
     const bool pre_on = HK_LOAD && p.hk.pre_mode != HOOK_NONE;  // wave-uniform
     // index (inside its transform) of the first sample of lane-load i of group h, and its tile column / row
@@ -575,6 +592,11 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     const int l0 = (g & cpr_mask) * V;
                     src = tc.in + (long long)t * p.in_c + (long long)(l0 >> p.in_blk_bits) * p.in_blk_stride +
                           (l0 & ((1 << p.in_blk_bits) - 1));
+                    if (HK_FRAMES) {  // frame f of the execute: signal f / frames_per_signal, frame f % frames_per_signal inside it
+                        const unsigned f = (unsigned)(tc.c0 + t), fps = (unsigned)p.hk.frames_per_signal;
+                        const unsigned sig = fps == 1u ? f : (unsigned)(((unsigned long long)f * p.hk.frames_rcp) >> 32);
+                        src = p.in + (long long)sig * p.hk.signal_pitch + (long long)(f - sig * fps) * p.in_c + l0;
+                    }
                 }
                 if (HK_LOAD) {
                     // zero padding: samples at or beyond n_in are not read; an fp32 pair that straddles the end, or rows
@@ -875,7 +897,22 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                         const int g = tid + i * nthreads;
                         const int t = h * CG + (g >> log2CPR);
                         const int pos = g & cpr_mask;
-                        if (tc.c0 + t < p.n_cols) {
+                        if (HK_POWER) {  // one-sided power of frame c0 + t: bins pos * V ... that are <= L/2, every store predicated
+                            const int half = L >> 1;
+                            if (tc.c0 + t < p.n_cols && pos * V <= half) {
+                                const vec16<T> v = *reinterpret_cast<const vec16<T>*>(smem + h * group_bytes + (size_t)(g >> log2CPR) * pitch + (size_t)pos * 16);
+                                T* row = p.hk.power_out + (long long)(tc.c0 + t) * (half + 1);
+                                FFT_UNROLL
+                                for (int vv = 0; vv < V; vv++) {
+                                    const int k = pos * V + vv;
+                                    if (k <= half) {
+                                        T pw = (v.c[vv].re * v.c[vv].re + v.c[vv].im * v.c[vv].im) * p.hk.power_scale;
+                                        if (k > 0 && k < half) pw *= (T)2;
+                                        row[k] = pw;
+                                    }
+                                }
+                            }
+                        } else if (tc.c0 + t < p.n_cols) {
                             vec16<T> v = *reinterpret_cast<const vec16<T>*>(smem + h * group_bytes + (size_t)(g >> log2CPR) * pitch + (size_t)pos * 16);
                             cpx<T>* dst = tc.out + (long long)t * p.out_c + (long long)pos * V;
                             if (HK_STORE) {  // the single-pass kernel's transforms are its columns: transform index = c0 + t

@@ -145,6 +145,23 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) psd_onesided_kernel(const cpx<T>* X, T* p
     }
 }
 
+// Welch average of periodograms: psd[s][k] = (1 / nw) * sum_w power[s][w][k], power: [signals][nw][hb] one-sided power rows
+// (hb = n/2 + 1), psd: [signals][hb].  One thread per output value, lanes along k (coalesced on both sides); w ascends inside the
+// thread and the sum is kept in double for both precisions (the kernel is memory bound, and the error must not grow with the
+// frame count).  No atomics: the result is bit-reproducible.  `total` = signals * hb.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_mean_kernel(const T* power, T* psd, int nw, int hb, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long s = i / hb;
+        const int k = (int)(i - s * hb);
+        const T* col = power + s * (long long)nw * hb + k;
+        double acc = 0.0;
+        for (int w = 0; w < nw; w++) acc += (double)col[(long long)w * hb];
+        psd[i] = (T)(acc / (double)nw);
+    }
+}
+
 // Device streams, 16 bytes per lane, `unroll` independent accesses in flight per thread, grid-stride: the practical ceiling
 // of the box the benchmark runs on (MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy).  MODE 0 copy, 1 read only (the
 // values are folded into one word that is stored only if it is a NaN pattern the inputs never hold), 2 write only.  NT: the

@@ -1,7 +1,8 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
-// reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram).  Templated on the same runtime
-// policy RT as the engine, so the unmodified source also runs in the CPU emulation (tests/emu).
+// reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
+// overlapping frames).  Templated on the same runtime policy RT as the engine, so the unmodified source also runs in the CPU
+// emulation (tests/emu).
 #pragma once
 
 #include "fft_engine.h"
@@ -378,6 +379,137 @@ class FusedPlan {
             }
             default: break;
         }
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Short-time transforms on overlapping frames: the STFT, the spectrogram (one periodogram per frame) and Welch's averaged
+// periodogram (reference applications/power_spectrum.c:87-130, welch_psd; windows :5-25, periodogram scaling :70-80).
+//   x: [n_signals] complex signals of signal_len samples, signal s at x + s * signal_pitch;
+//   frame w of a signal = its samples w * hop ... w * hop + n - 1, w < nw = (signal_len - (n - hop)) / hop (:92-93): no frame
+//   reaches past signal_len (the reference's zero-fill branch :105-109 is dead), trailing samples that fill no frame are ignored;
+//   FRAMES_STFT   out[s][w][k] = FFT_n(window * frame)[k]                        complex, unscaled
+//   FRAMES_POWER  out[s][w][k] = |.|^2 / (sample_rate * P), doubled for 0 < k < n/2, k <= n/2     real
+//   FRAMES_WELCH  out[s][k]    = mean over w of the POWER rows                                     real
+//   P = 0.375 n for the Hann window (hard-coded in the reference, :72; FUSED_PSD uses the same), sum w[i]^2 otherwise.
+// n a power of two that fits ONE hook-capable pass: one launch of the hooked single-pass kernel with the framed load (frames of
+// all signals are its tile columns; the window is its load-side table; POWER / WELCH: its one-sided power store), Welch adds
+// frames_mean_kernel.  Every other n, and no_fusion: per signal one execute_hooked with in_pitch = hop (pad_mul_kernel + a plain
+// execute where the core has no hooks or a signal does not start 16-byte aligned), psd_onesided_kernel, frames_mean_kernel --
+// a correct fallback, not a tuned one.
+// ---------------------------------------------------------------------------
+enum FramesWindow { WINDOW_RECT = 0, WINDOW_HANN = 1, WINDOW_HAMMING = 2, WINDOW_BLACKMAN = 3, WINDOW_USER = 4 };
+enum FramesOut { FRAMES_STFT = 0, FRAMES_POWER = 1, FRAMES_WELCH = 2 };
+
+template <typename T, typename RT>
+class FramesPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    RT* rt = nullptr;
+    int n = 0, hop = 0, signal_len = 0, n_signals = 0, nw = 0, window = 0, out_kind = 0;
+    long double window_power = 1.0L;  // P
+    Pow2Plan<T, RT> core;
+    cpx<T>* win = nullptr;    // the window as complex values, + 1 padding entry (ExecHooks::pre_tab)
+    T* power = nullptr;       // WELCH: [n_signals * nw][n/2 + 1]
+    cpx<T>* work = nullptr;   // fallback, POWER / WELCH: the complex rows [n_signals * nw][n] (allocated at its first use)
+    bool ok = false;
+    bool no_fusion = false;
+    ~FramesPlan() {
+        if (!rt) return;
+        rt->dfree(win); rt->dfree(power); rt->dfree(work);
+    }
+    long long frames() const { return (long long)n_signals * nw; }
+    int bins() const { return n / 2 + 1; }
+    bool fused() const { return ok && !no_fusion && core.round_capable() && core.frames_exact(frames(), nw); }
+
+    // w_host: n window values of type T (WINDOW_USER), ignored otherwise
+    bool build(RT* runtime, int n_, int hop_, int signal_len_, int n_signals_, int window_, const T* w_host, int out_kind_) {
+        rt = runtime; n = n_; hop = hop_; signal_len = signal_len_; n_signals = n_signals_; window = window_; out_kind = out_kind_;
+        if (n < 2 || (n & (n - 1)) != 0 || n > (1 << 29) || hop < 1 || hop > n || signal_len < n || n_signals < 1) return false;
+        if (window < WINDOW_RECT || window > WINDOW_USER || (window == WINDOW_USER && !w_host)) return false;
+        if (out_kind < FRAMES_STFT || out_kind > FRAMES_WELCH) return false;
+        nw = (signal_len - (n - hop)) / hop;
+        if (nw < 1 || frames() > 0x7fffffff || frames() * (long long)n > (1ll << 40)) return false;
+        core.wants_hooks = true;
+        if (!core.build(rt, ilog2(n), ALGO_AUTO, (int)frames())) return false;
+        // the reference's windows with their n - 1 denominators (power_spectrum.c:5-25), as complex values; + 1 padding entry
+        std::vector<cpx<T>> wv((size_t)n + 1);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        long double sum2 = 0.0L;
+        for (int i = 0; i < n; i++) {
+            const long double a = two_pi * (long double)i / (long double)(n - 1);
+            long double w = 1.0L;
+            if (window == WINDOW_HANN) w = 0.5L * (1.0L - cosl(a));
+            else if (window == WINDOW_HAMMING) w = 0.54L - 0.46L * cosl(a);
+            else if (window == WINDOW_BLACKMAN) w = 0.42L - 0.5L * cosl(a) + 0.08L * cosl(2.0L * a);
+            else if (window == WINDOW_USER) w = (long double)w_host[i];
+            sum2 += w * w;
+            wv[(size_t)i].re = (T)w;
+            wv[(size_t)i].im = 0;
+        }
+        wv[(size_t)n] = wv[0];
+        window_power = window == WINDOW_HANN ? 0.375L * (long double)n : sum2;
+        if (out_kind != FRAMES_STFT && !(window_power > 0.0L)) return false;
+        win = (cpx<T>*)rt->dmalloc(wv.size() * SZ);
+        if (!win) return false;
+        rt->h2d(win, wv.data(), wv.size() * SZ);
+        if (out_kind == FRAMES_WELCH) {
+            power = (T*)rt->dmalloc((size_t)frames() * (size_t)bins() * sizeof(T));
+            if (!power) return false;
+        }
+        ok = true;
+        return true;
+    }
+
+    // x: the signals (signal_pitch elements apart; 0: signal_len); out: see FramesOut.  0 / -1 (bad arguments: nothing is launched)
+    int execute(const cpx<T>* x, long long signal_pitch, void* out, double sample_rate) {
+        if (!ok || !x || !out || (const void*)x == (const void*)out) return -1;
+        if (signal_pitch == 0) signal_pitch = signal_len;
+        if (signal_pitch < signal_len) return -1;
+        const long long nf = frames();
+        const int hb = bins();
+        const T scale = (T)(1.0L / ((long double)sample_rate * window_power));
+        T* rows = out_kind == FRAMES_WELCH ? power : (T*)out;  // where the power rows go
+        if (fused()) {
+            ExecHooks<T> f;
+            f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL;
+            f.n_in = n; f.in_pitch = hop;
+            f.frames_per_signal = nw; f.signal_pitch = signal_pitch;
+            if (out_kind == FRAMES_STFT) {
+                core.execute_frames(x, (cpx<T>*)out, (int)nf, f);
+            } else {
+                f.power_out = rows; f.power_scale = scale;
+                core.execute_frames(x, reinterpret_cast<cpx<T>*>(rows), (int)nf, f);  // (complex `out` unused: the power store replaces it)
+            }
+        } else {
+            cpx<T>* stage = (cpx<T>*)out;
+            if (out_kind != FRAMES_STFT) {
+                if (!work) work = (cpx<T>*)rt->dmalloc((size_t)nf * (size_t)n * SZ);
+                if (!work) return -1;
+                stage = work;
+            }
+            const bool aligned = (signal_pitch % V) == 0 && ((uintptr_t)x & 15) == 0;  // every signal starts 16-byte aligned
+            if (core.hook_capable() && aligned) {
+                ExecHooks<T> f;
+                f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL;
+                f.n_in = n; f.in_pitch = hop;
+                for (int s = 0; s < n_signals; s++)
+                    core.execute_hooked(x + (long long)s * signal_pitch, stage + (long long)s * nw * n, nw, false, f);
+            } else {
+                const unsigned per_block = 256 * BLU_PER_THREAD;
+                const unsigned bpr = (unsigned)(((long long)n + per_block - 1) / per_block);
+                for (int s = 0; s < n_signals; s++)
+                    rt->launch(fftk::pad_mul_kernel<T>, (long long)bpr * nw, 256, (size_t)0, x + (long long)s * signal_pitch, (long long)hop, n,
+                               (const cpx<T>*)win, (int)fftk::HOOK_MUL, stage + (long long)s * nw * n, n, bpr);
+                core.execute(stage, stage, (int)nf, false);
+            }
+            if (out_kind != FRAMES_STFT)
+                launch_flat(rt, fftk::psd_onesided_kernel<T>, nf * hb, (const cpx<T>*)stage, rows, n, scale, nf * hb);
+        }
+        if (out_kind == FRAMES_WELCH)
+            launch_flat(rt, fftk::frames_mean_kernel<T>, (long long)n_signals * hb, (const T*)power, (T*)out, nw, hb, (long long)n_signals * hb);
+        return 0;
     }
 };
 

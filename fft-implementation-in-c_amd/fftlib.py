@@ -66,6 +66,8 @@ SIGNATURES = {
     "fft_gpu_plan_r2c_1d_algo_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_1d_algo_hip": (_vp, [_i, _i, _i, _i]),
     "fft_gpu_plan_fused_hip": (_vp, [_i, _i, _i, _vp, _i, _i]), "fft_gpu_fused_out_len_hip": (_i, [_vp]),
     "fft_gpu_execute_fused_hip": (_i, [_vp, _vp, _vp, _vp, C.c_double]),
+    "fft_gpu_plan_frames_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count_hip": (_i, [_vp]),
+    "fft_gpu_execute_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -86,6 +88,8 @@ SIGNATURES = {
     "fft_gpu_execute_timed": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_float)]),
     "fft_gpu_dft_1d_f32": (_i, [_vp, _vp, _i, _i]), "fft_gpu_dft_1d_batch_f32": (_i, [_vp, _vp, _i, _i, _i]),
     "fft_gpu_bit_reverse": (_i, [_vp, _vp, _i, _i, _i]),
+    "fft_gpu_plan_frames": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count": (_i, [_vp]),
+    "fft_gpu_execute_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -99,6 +103,7 @@ SIGNATURES = {
     "fft_convolution_gpu": (_i, [_vp, _i, _vp, _i, _vp]), "circular_convolution_gpu": (_i, [_vp, _vp, _i, _vp]),
     "compute_periodogram_gpu": (_vp, [_vp, _i, C.c_double]), "autocorrelation_fft_gpu": (_vp, [_vp, _i]),
     "cross_correlation_fft_gpu": (_vp, [_vp, _vp, _i]),
+    "fft_welch_psd_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -267,6 +272,8 @@ class Plan:
 
 
 FUSED_KINDS = {"conv": 0, "circ": 1, "autocorr": 2, "xcorr": 3, "psd": 4}
+WINDOWS = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3, "user": 4}
+FRAMES_OUT = {"stft": 0, "power": 1, "welch": 2}
 
 
 class ExtPlan:
@@ -299,6 +306,37 @@ class ExtPlan:
                                               None if hh is None else hh.ctypes.data, batch, _prec_of(dt)))
         p.out_len = p.lib.fft_gpu_fused_out_len_hip(p.handle)
         return p
+
+    @classmethod
+    def frames(cls, n, hop, signal_len, n_signals=1, window="hann", out="stft", dtype=np.complex128):
+        """STFT / spectrogram ("power") / Welch plan on overlapping frames.  window: a name of WINDOWS, or n real values (USER)."""
+        dt = np.dtype(dtype)
+        w = None
+        if not isinstance(window, str):
+            w = np.ascontiguousarray(np.asarray(window).astype(np.float32 if dt == np.complex64 else np.float64))
+            if w.shape != (n,):
+                raise ValueError("a user window has n values")
+        p = cls(init().fft_gpu_plan_frames_hip(n, hop, signal_len, n_signals, WINDOWS["user" if w is not None else window],
+                                               None if w is None else w.ctypes.data, FRAMES_OUT[out], _prec_of(dt)))
+        p.n, p.n_signals, p.out, p.dtype = n, n_signals, out, dt
+        p.nw = p.lib.fft_gpu_frames_count_hip(p.handle)
+        return p
+
+    def frames_out(self):
+        """(shape, dtype) of a frames plan's result."""
+        rdt = np.dtype(np.float32 if self.dtype == np.complex64 else np.float64)
+        if self.out == "stft":
+            return (self.n_signals, self.nw, self.n), self.dtype
+        if self.out == "power":
+            return (self.n_signals, self.nw, self.n // 2 + 1), rdt
+        return (self.n_signals, self.n // 2 + 1), rdt
+
+    def set_stream(self, stream_ptr):
+        self.lib.fft_gpu_plan_set_stream(self.handle, stream_ptr)
+
+    def execute_frames(self, d_x, d_out, signal_pitch=0, sample_rate=1.0):
+        if self.lib.fft_gpu_execute_frames_hip(self.handle, d_x, signal_pitch, d_out, sample_rate) != 0:
+            raise RuntimeError("fft_gpu_execute_frames_hip failed")
 
     def execute_ptr(self, d_in, d_out):
         if self.lib.fft_gpu_execute_ptr(self.handle, d_in, d_out) != 0:
@@ -404,6 +442,39 @@ def fused(kind, x, y=None, h=None, fs=1.0):
     res = _roundtrip(plan, x, (batch, plan.out_len), odt, y=yy, fused=True, fs=fs)
     plan.destroy()
     return res
+
+
+def _frames(x, n, hop, window, out, fs):
+    x = np.ascontiguousarray(x)
+    x2 = x.reshape(1, -1) if x.ndim == 1 else x
+    plan = ExtPlan.frames(n, hop, x2.shape[1], x2.shape[0], window, out, x2.dtype)
+    shape, odt = plan.frames_out()
+    a, o = DeviceBuffer(x2.nbytes), DeviceBuffer(int(np.prod(shape)) * odt.itemsize)
+    a.upload(x2)
+    plan.execute_frames(a.ptr, o.ptr, 0, fs)
+    if plan.sync() != 0:
+        raise RuntimeError("execute failed")
+    res = o.download(shape, odt)
+    a.free()
+    o.free()
+    plan.destroy()
+    return res[0] if x.ndim == 1 else res
+
+
+def stft(x, n, hop, window="hann"):
+    """x: [signals, len] (or [len]) complex -> [signals, frames, n] complex: the transform of every windowed frame
+    x[s, w * hop : w * hop + n], frames = (len - (n - hop)) // hop; window: a name of WINDOWS or n real values."""
+    return _frames(x, n, hop, window, "stft", 1.0)
+
+
+def spectrogram(x, n, hop, window="hann", fs=1.0):
+    """-> [signals, frames, n//2 + 1] real: the one-sided periodogram of every frame."""
+    return _frames(x, n, hop, window, "power", fs)
+
+
+def welch(x, n, hop, window="hann", fs=1.0):
+    """-> [signals, n//2 + 1] real: Welch's PSD, the mean of the frames' periodograms."""
+    return _frames(x, n, hop, window, "welch", fs)
 
 
 def fft(x, direction=FFT_FORWARD, algo=ALGO_AUTO, inplace=True):

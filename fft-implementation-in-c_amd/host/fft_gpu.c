@@ -186,6 +186,20 @@ int fft_gpu_bit_reverse(fft_gpu_memory_t in, fft_gpu_memory_t out, int n, int ba
     return fft_gpu_bit_reverse_hip(fft_gpu_memory_ptr_hip(in), fft_gpu_memory_ptr_hip(out), n, batch, prec, NULL);
 }
 
+/* STFT / spectrogram / Welch plans on overlapping frames */
+fft_gpu_plan_t fft_gpu_plan_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                   fft_gpu_frames_out_t out, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_frames")) return NULL;
+    return fft_gpu_plan_frames_hip(n, hop, signal_len, n_signals, window, w_host, out, prec);
+}
+
+int fft_gpu_frames_count(fft_gpu_plan_t plan) { return fft_gpu_frames_count_hip(plan); }
+
+int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch, void* d_out, double sample_rate) {
+    if (!backend_is_hip("fft_gpu_execute_frames")) return -1;
+    return fft_gpu_execute_frames_hip(plan, d_x, signal_pitch, d_out, sample_rate);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

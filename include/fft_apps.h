@@ -6,6 +6,7 @@
  *   fft_convolution, circular_convolution      applications/convolution.c:34-96
  *   compute_periodogram, autocorrelation_fft,
  *   cross_correlation_fft                      applications/power_spectrum.c:58-86, 133-190
+ *   welch_psd (here fft_welch_psd_gpu)         applications/power_spectrum.c:87-130
  * with a `_gpu` suffix, host arrays in and out, and int 0 / -1 (or NULL) instead of exit().  Each is ONE fused plan on the
  * device (fft_hip.h: fft_gpu_plan_fused_hip): forward transform, element-wise step and inverse transform, with the zero
  * padding, the spectral product and the truncation riding on the FFT passes.  Batched, device-resident use goes through
@@ -29,6 +30,11 @@ double* compute_periodogram_gpu(const complex_t* signal, int n, double sample_ra
 /* first n lags; a malloc'd (allocate_complex_array) array freed by the caller; NULL on failure */
 complex_t* autocorrelation_fft_gpu(const complex_t* signal, int n);
 complex_t* cross_correlation_fft_gpu(const complex_t* x, const complex_t* y, int n);
+/* Welch's averaged Hann periodogram (welch_psd, applications/power_spectrum.c:87-130, its params struct flattened): windows of
+ * window_size samples (a power of two) every window_size - overlap samples, 0 <= overlap < window_size <= signal_len; a malloc'd
+ * array of window_size/2 + 1 doubles freed by the caller; NULL on failure.  ONE frames plan (fft_gpu_plan_frames_hip): the windows
+ * are read in place on the device, nothing is copied per window. */
+double* fft_welch_psd_gpu(const complex_t* signal, int signal_len, double sample_rate, int window_size, int overlap);
 
 #ifdef __cplusplus
 }

@@ -112,7 +112,8 @@ typedef enum {
                                             touched) and the multi-pass plan queued behind it does the work */
     FFT_GPU_OPT_TEAM_ENABLE = 2,         /* 0: run the multi-pass schedule only; 1: back to the team kernel where the plan has one */
     FFT_GPU_OPT_NO_FUSION = 3,           /* 1: Bluestein / fused-consumer plans run their element-wise steps as kernels of their own
-                                            instead of fusing them into the FFT passes (same results to rounding; tests) */
+                                            instead of fusing them into the FFT passes (same results to rounding; tests); frames plans
+                                            run their per-signal fallback */
     FFT_GPU_OPT_NO_CHAIN = 4,            /* 1: Bluestein / fused-consumer plans keep the forward transform's last pass and the inverse
                                             transform's first pass as two kernels (by default they run as one where their tiles agree
                                             and the transform has >= 2^19 points; tests); 2: as one wherever the tiles agree (tools) */
@@ -130,6 +131,14 @@ typedef enum {
     FFT_GPU_FUSED_XCORR = 3,         /* first nx lags of IFFT(conj(FFT(x)) FFT(y))                       power_spectrum.c:161-190 */
     FFT_GPU_FUSED_PSD = 4            /* one-sided Hann periodogram, nx/2 + 1 REAL values (nx a power of two) power_spectrum.c:58-86 */
 } fft_gpu_fused_t;
+
+/* Short-time transforms on overlapping frames (reference applications/power_spectrum.c:87-130, welch_psd, and what it is the
+ * segmented form of): frame w of a signal is its samples w * hop ... w * hop + n - 1, windowed and transformed. */
+typedef enum { FFT_GPU_WINDOW_RECT = 0, FFT_GPU_WINDOW_HANN = 1, FFT_GPU_WINDOW_HAMMING = 2,
+               FFT_GPU_WINDOW_BLACKMAN = 3, FFT_GPU_WINDOW_USER = 4 } fft_gpu_window_t; /* the reference's formulas, n - 1 denominators: power_spectrum.c:5-25 */
+typedef enum { FFT_GPU_FRAMES_STFT = 0,    /* [S][nw][n] complex, unscaled */
+               FFT_GPU_FRAMES_POWER = 1,   /* [S][nw][n/2 + 1] real: one periodogram per frame */
+               FFT_GPU_FRAMES_WELCH = 2 }  /* [S][n/2 + 1] real: their mean over the frames */ fft_gpu_frames_out_t;
 
 /* backend-level additive entry points */
 int fft_gpu_device_count_hip(void);
@@ -181,6 +190,23 @@ int fft_gpu_fused_out_len_hip(fft_gpu_plan_t plan); /* elements per output row (
 /* async on the plan's stream.  d_x: [batch][nx] complex; d_y: the second signal of FFT_GPU_FUSED_XCORR, else NULL;
  * d_out: [batch][out_len]; sample_rate scales FFT_GPU_FUSED_PSD only */
 int fft_gpu_execute_fused_hip(fft_gpu_plan_t plan, const void* d_x, const void* d_y, void* d_out, double sample_rate);
+/* STFT, spectrogram and Welch PSD of n_signals complex signals of signal_len samples.  n: the frame length, a power of two >= 2;
+ * 1 <= hop <= n; signal_len >= n; anything else returns NULL.  Every signal has nw = (signal_len - (n - hop)) / hop frames
+ * (power_spectrum.c:92-93); no frame reaches past signal_len, trailing samples that fill no whole frame are ignored.
+ * w_host: the n window values (host memory, reals of `prec`) of FFT_GPU_WINDOW_USER, else ignored.  POWER and WELCH rows are
+ * |X[k]|^2 / (sample_rate * P), doubled for 0 < k < n/2 (power_spectrum.c:72-80), P = 0.375 n for the Hann window (the
+ * reference's constant, as in FFT_GPU_FUSED_PSD) and sum w[i]^2 for every other window.  Where n fits one hooked pass the
+ * frames are read in place by ONE launch (no [frames][n] copy), windowed on the way in, and POWER / WELCH rows leave that launch
+ * as reals; WELCH adds the mean kernel (double accumulation, no atomics: bit-reproducible).  Every other n, and
+ * FFT_GPU_OPT_NO_FUSION: one hooked execute per signal, a power kernel, the mean.  fft_gpu_plan_info_hip: n, batch = n_signals * nw,
+ * the core's passes, fused = 1 when the framed load and the stores ride on the pass.  Sync, set_stream, destroy as for fused plans. */
+fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window,
+                                       const void* w_host /* n reals of prec, USER only */, fft_gpu_frames_out_t out, fft_precision_t prec);
+int fft_gpu_frames_count_hip(fft_gpu_plan_t plan);   /* nw = (signal_len - (n - hop)) / hop; -1: not a frames plan */
+/* async on the plan's stream.  d_x: complex signals, signal s at d_x + s * signal_pitch elements (0: signal_len; < signal_len: -1);
+ * d_out: see fft_gpu_frames_out_t; it must not overlap d_x (d_out == d_x returns -1); sample_rate scales POWER and WELCH only */
+int fft_gpu_execute_frames_hip(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch /* 0: signal_len */,
+                               void* d_out, double sample_rate);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
@@ -248,6 +274,11 @@ int fft_gpu_execute_timed(fft_gpu_plan_t plan, const void* d_in, void* d_out, in
 int fft_gpu_dft_1d_f32(complex32_t* in, complex32_t* out, int n, fft_direction direction);
 int fft_gpu_dft_1d_batch_f32(complex32_t* in, complex32_t* out, int n, int batch, fft_direction direction);
 int fft_gpu_bit_reverse(fft_gpu_memory_t in, fft_gpu_memory_t out, int n, int batch, fft_precision_t prec);
+/* frames plans (fft_gpu_plan_frames_hip above) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                   fft_gpu_frames_out_t out, fft_precision_t prec);
+int fft_gpu_frames_count(fft_gpu_plan_t plan);
+int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch, void* d_out, double sample_rate);
 
 #ifdef __cplusplus
 }
