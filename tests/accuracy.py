@@ -77,15 +77,21 @@ TWO_TONE_K = {
 }
 CAP = {"bluestein": 64, "fused_conv": 64, "fused_corr": 64, "psd": 64}
 POW2_CAP = 16
+# Unit impulses against the closed-form column of the DFT matrix (tests/operator_ladder.py; check_rows(kind="impulse")): the bound
+# is the family's BOUND_K unless a family is pinned here with a K of its own (at least twice its measured value, within the caps).
+# The measured column is operator_ladder.MEASURED; no family needs an entry.
+IMPULSE_K = {}
 
 # worst measured e_b / (u * log2 n) per (family, precision) in this process; FFT_ACCURACY_REPORT=<file> writes it out as JSON
 WORST = {}
 
 
-def bound(family, dtype, n, m=None):
-    """K * u * log2(n) (log2(m) for Bluestein, m = the padded power-of-two length)."""
+def bound(family, dtype, n, m=None, kind=None):
+    """K * u * log2(n) (log2(m) for Bluestein, m = the padded power-of-two length).  kind="impulse": K from IMPULSE_K where the
+    family has an entry there."""
     length = m if m else n
-    return BOUND_K[family] * U[np.dtype(dtype)] * max(1.0, np.log2(length))
+    K = IMPULSE_K.get(family, BOUND_K[family]) if kind == "impulse" else BOUND_K[family]
+    return K * U[np.dtype(dtype)] * max(1.0, np.log2(length))
 
 
 def bound_two_tone(family, dtype, n):
@@ -268,16 +274,21 @@ def assert_within(e, k, limit, label, b0=0):
            " ..." if bad.size > 12 else "", q[0], q[1], q[2], q[3], int(e.size - fin.size)))
 
 
-def check_rows(y, x, direction, family, dtype=None, n=None, m=None, label="", ref=None, b0=0, long_rows=0, scale="rms"):
+def check_rows(y, x, direction, family, dtype=None, n=None, m=None, label="", ref=None, b0=0, long_rows=0, scale="rms", kind=None):
     """Check result rows y of input rows x against the reference: e_b <= bound(family) for every row.  Returns e.
-    scale: the unit of a bin's error, see row_errors().
+    scale: the unit of a bin's error, see row_errors().  kind (e.g. "impulse"): the worst value is recorded under
+    "<kind>:<family>" and the bound is bound(family, kind=kind).
     long_rows > 0 (fp64 results): also compare the first rows with a long-double reference, and show that the float64
     reference's own error is below a quarter of the bound."""
     dtype = np.dtype(dtype or y.dtype)
     n = n or y.shape[-1]
-    lim = bound(family, dtype, n, m)
+    lim = bound(family, dtype, n, m, kind)
     e, k = errors_vs(y, x, direction, ref, scale=scale)
-    _note(family, dtype, n, m, e)
+    _note("%s:%s" % (kind, family) if kind else family, dtype, n, m, e)
+    if kind and e.size:  # the figure before anything asserts on it
+        w = int(np.argmax(np.where(np.isnan(e), np.inf, e)))
+        print("%s %s %s: worst e / (u log2 %s) = %.3f (row %d, bin %d)" % (kind, label, np.dtype(dtype).name, "m" if m else "n",
+              float(e[w]) / (U[np.dtype(dtype)] * max(1.0, np.log2(m if m else n))), b0 + w, int(k[w])))
     assert_within(e, k, lim, "%s %s n=%d dir=%+d" % (label, family, n, direction), b0)
     if long_rows and ref is None:
         rows = min(long_rows, y.shape[0])
@@ -403,7 +414,7 @@ def input_unchanged(g, x):
     return True
 
 
-def check_device_rows(g, x, direction, family, out_dtype=None, out_width=None, m=None, label="", ref=None, long_rows=0):
+def check_device_rows(g, x, direction, family, out_dtype=None, out_width=None, m=None, label="", ref=None, long_rows=0, kind=None):
     """Download the result rows of g in slices and check every one against the reference of the matching rows of x."""
     dt = np.dtype(out_dtype or x.dtype)
     width = out_width or x.shape[1]
@@ -413,7 +424,7 @@ def check_device_rows(g, x, direction, family, out_dtype=None, out_width=None, m
         cnt = min(step, g.rows - r0)
         y = g.rows_at(r0, cnt, dt, width)
         es.append(check_rows(y, x[r0:r0 + cnt], direction, family, dt, n=max(width, x.shape[1]), m=m, label=label, ref=ref, b0=r0,
-                             long_rows=long_rows if r0 == 0 else 0))
+                             long_rows=long_rows if r0 == 0 else 0, kind=kind))
     return np.concatenate(es)
 
 
@@ -499,14 +510,14 @@ def check_execute_streamed(plan, n, batch, dtype, seed, family, direction=None, 
                 g.free()
 
 
-def check_execute(plan, x, family, direction=None, inplace=True, m=None, label="", expect=None, long_rows=0, ref=None):
+def check_execute(plan, x, family, direction=None, inplace=True, m=None, label="", expect=None, long_rows=0, ref=None, kind=None):
     """Run the batch x through plan (raw-pointer execute, out of place into a guarded NaN-filled output) and check
       - every transform: e_b <= bound(family) (fp64 and long_rows > 0: the first rows also against a long-double reference),
       - the input bytes are unchanged,
       - both guard rows still hold the sentinel;
     inplace=True: also in place (guarded too), bit-identical to the out-of-place result.
     expect: a callable run after each sync (asserts on plan.team_status() / plan.info()); ref: the reference of a row batch
-    (default: the 1D transform of every row).  Returns e of the out-of-place run."""
+    (default: the 1D transform of every row); kind: see check_rows().  Returns e of the out-of-place run."""
     direction = plan.direction if direction is None else direction
     batch, n = x.shape
     rb = n * x.dtype.itemsize
@@ -523,7 +534,7 @@ def check_execute(plan, x, family, direction=None, inplace=True, m=None, label="
         assert gout.guards_intact(), "%s: out-of-place execute wrote outside [out, out + batch * n)" % label
         assert gin.guards_intact(), "%s: out-of-place execute wrote next to its input" % label
         assert input_unchanged(gin, x), "%s: out-of-place execute changed its input" % label
-        e = check_device_rows(gout, x, direction, family, m=m, label=label + " out-of-place", ref=ref, long_rows=long_rows)
+        e = check_device_rows(gout, x, direction, family, m=m, label=label + " out-of-place", ref=ref, long_rows=long_rows, kind=kind)
         gin.free()
         gin = None
         if inplace:
@@ -549,7 +560,7 @@ def _flat_rows(ptr, r0, cnt, dtype, width):
 
 
 def check_execute_io(run, x, w_out, dtype_out, family, ref, x2=None, n=None, m=None, scale="rms", inplace=False, label="",
-                     expect=None, expected=None):
+                     expect=None, expected=None, kind=None):
     """check_execute() for executes whose input and output rows differ in width or type (2D, r2c, c2r, fused consumers).
       x: input rows [batch][w_in]; x2: optional second input of the same shape (cross-correlation's y);
       run(in_ptr, in2_ptr, out_ptr): enqueue the execute and wait for it (in2_ptr is None without x2);
@@ -605,7 +616,7 @@ def check_execute_io(run, x, w_out, dtype_out, family, ref, x2=None, n=None, m=N
             cnt = min(step, batch - r0)
             y = gout.rows_at(r0, cnt, dt_out, w_out)
             es.append(check_rows(y, xx[r0:r0 + cnt], 0, family, dt_out, n=n, m=m, label=label + " out-of-place", ref=ref_rows, b0=r0,
-                                 scale=scale))
+                                 scale=scale, kind=kind))
         e = np.concatenate(es)
         gin.free()
         gin = None
@@ -631,3 +642,162 @@ def check_execute_io(run, x, w_out, dtype_out, family, ref, x2=None, n=None, m=N
         for g in (gin, gin2, gout, gip):
             if g is not None:
                 g.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# exact conditions on a linear operator: neighbours of a poisoned transform, power-of-two scaling, zeros
+# ---------------------------------------------------------------------------------------------------------------------------
+POISONS = ("nan", "inf0", "huge")
+# "huge": every sample 2^120 / 2^1000, finite.  A transform's bin 0 is n times that and overflows only from n = 256 in fp32 (never in
+# fp64 at the sizes used); the quadratic consumers (autocorr, xcorr, psd, conv products) overflow at every n.  Below that the row is
+# a finite value 2^100 and more above its neighbours', which a lane that adds or multiplies where it should select cannot absorb.
+HUGE_EXP = {np.dtype(np.float32): 120, np.dtype(np.float64): 1000}
+SCALE_EXP = {np.dtype(np.float32): 20, np.dtype(np.float64): 200}   # check_scaling: s = +-20 in fp32, +-200 in fp64
+
+
+def poisoned(x, rows, poison):
+    """A copy of x whose `rows` are poisoned: "nan" every sample NaN; "inf0" the real part of sample 0 +Inf, the rest untouched;
+    "huge" every sample 2^120 (fp32) / 2^1000 (fp64)."""
+    x = np.array(x, copy=True, order="C")
+    v = x.view(x.real.dtype).reshape(x.shape[0], -1)
+    rows = np.asarray(sorted(rows), dtype=np.int64)
+    if poison == "nan":
+        v[rows] = np.nan
+    elif poison == "inf0":
+        v[rows, 0] = np.inf
+    elif poison == "huge":
+        v[rows] = np.ldexp(1.0, HUGE_EXP[v.dtype])
+    else:
+        raise ValueError("poison: one of %s" % (POISONS,))
+    return x
+
+
+class _Runs:
+    """Repeated runs of run(in_ptr, in2_ptr, out_ptr) on ONE set of guarded buffers: every call uploads its inputs, NaN-fills the
+    output, runs, and checks the guards and the untouched inputs.  Returns the result rows [rows_out][w_out]."""
+
+    def __init__(self, run, x, w_out, dtype_out, rows_out, x2, label):
+        self.run, self.label = run, label
+        self.w_out, self.dt_out, self.rows_out = w_out, np.dtype(dtype_out), rows_out
+        self.gin = Guarded(x.shape[0], x.shape[1] * x.dtype.itemsize, align16=True)
+        self.gin2 = Guarded(x2.shape[0], x2.shape[1] * x2.dtype.itemsize, align16=True) if x2 is not None else None
+        self.gout = Guarded(rows_out, w_out * self.dt_out.itemsize, align16=True)
+
+    def __call__(self, x, x2=None):
+        upload_rows(self.gin, np.ascontiguousarray(x))
+        if self.gin2:
+            upload_rows(self.gin2, np.ascontiguousarray(x2))
+        self.gout.fill(np.full(self.w_out, np.nan, dtype=self.dt_out))
+        self.run(self.gin.ptr, self.gin2.ptr if self.gin2 else None, self.gout.ptr)
+        assert self.gout.guards_intact(), "%s: the execute wrote outside its output" % self.label
+        assert self.gin.guards_intact(), "%s: the execute wrote next to its input" % self.label
+        assert input_unchanged(self.gin, x), "%s: the execute changed its input" % self.label
+        if self.gin2:
+            assert self.gin2.guards_intact(), "%s: the execute wrote next to its second input" % self.label
+            assert input_unchanged(self.gin2, x2), "%s: the execute changed its second input" % self.label
+        return self.gout.rows_at(0, self.rows_out, self.dt_out, self.w_out)
+
+    def free(self):
+        for g in (self.gin, self.gin2, self.gout):
+            if g is not None:
+                g.free()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[0], -1)
+
+
+def _differing_rows(a, b):
+    return np.flatnonzero(np.any(_bits(a) != _bits(b), axis=1))
+
+
+def check_neighbours(run, x, poison_rows, poison, w_out=None, dtype_out=None, x2=None, poison_second=False, out_rows=None,
+                     rows_out=None, label=""):
+    """A poisoned transform leaves its neighbours bit-identical.
+      run(in_ptr, in2_ptr, out_ptr): one execute of ONE plan, finished when it returns (as check_execute_io's);
+      x [batch][w_in] (x2: a second input of the same shape); poison_rows: the input rows replaced by `poison` (see poisoned())
+      in x -- poison_second=True: in x2 instead -- for the second run, on the same buffers;
+      w_out / dtype_out / rows_out: the result rows (default: as the input); out_rows(b): the result rows input row b feeds
+      (default: row b alone; a frames plan: the frames of signal b).
+    Every result row no poisoned input row feeds must equal the first run's bit for bit; under the "nan" poison every bin of every
+    fed row must be non-finite; guards intact, inputs unchanged.  Bit identity is a condition, not a tolerance: the same plan at
+    the same position sees the same data in every untouched row.  Returns (first result, second result)."""
+    x = np.ascontiguousarray(x)
+    w_out, dtype_out = w_out or x.shape[1], np.dtype(dtype_out or x.dtype)
+    rows_out = rows_out or x.shape[0]
+    out_rows = out_rows or (lambda b: (b,))
+    label = "%s poison=%s rows %s" % (label, poison, sorted(poison_rows))
+    r = _Runs(run, x, w_out, dtype_out, rows_out, x2, label)
+    try:
+        y0 = r(x, x2)
+        assert np.all(np.isfinite(y0)), "%s: the unpoisoned run is not finite" % label
+        if poison_second:
+            y1 = r(x, poisoned(x2, poison_rows, poison))
+        else:
+            y1 = r(poisoned(x, poison_rows, poison), x2)
+    finally:
+        r.free()
+    fed = np.zeros(rows_out, dtype=bool)
+    for b in poison_rows:
+        fed[list(out_rows(b))] = True
+    bad = [int(i) for i in _differing_rows(y0, y1) if not fed[i]]
+    if bad:
+        i = bad[0]
+        k = int(np.flatnonzero(np.any(_bits(y0[i].reshape(w_out, 1)) != _bits(y1[i].reshape(w_out, 1)), axis=1))[0])
+        raise AccuracyError("%s: %d untouched result rows changed with their neighbour: rows %s%s; row %d bin %d was %r, is %r"
+                            % (label, len(bad), bad[:12], " ..." if len(bad) > 12 else "", i, k, y0[i, k], y1[i, k]))
+    if poison == "nan":
+        clean = np.flatnonzero(fed & np.any(np.isfinite(y1), axis=1))
+        if clean.size:
+            i = int(clean[0])
+            raise AccuracyError("%s: result row %d of an all-NaN transform has %d finite bins (first: bin %d)"
+                                % (label, i, int(np.sum(np.isfinite(y1[i]))), int(np.flatnonzero(np.isfinite(y1[i]))[0])))
+    return y0, y1
+
+
+def check_scaling(run, x, degree=1, w_out=None, dtype_out=None, x2=None, rows_out=None, label=""):
+    """execute(2^s x) == 2^(s * degree) execute(x) bit for bit, s = +-SCALE_EXP (20 in fp32, 200 in fp64); degree 2: results
+    quadratic in x (autocorrelation, power).  x2 is not scaled.  The data path is mul / add / fma only, so a power of two commutes
+    with every rounding as long as nothing leaves the normal range; a hidden absolute threshold or a lossy intermediate breaks it."""
+    x = np.ascontiguousarray(x)
+    w_out, dtype_out = w_out or x.shape[1], np.dtype(dtype_out or x.dtype)
+    rows_out = rows_out or x.shape[0]
+    s = SCALE_EXP[np.dtype(x.real.dtype)]
+    r = _Runs(run, x, w_out, dtype_out, rows_out, x2, label)
+    try:
+        y0 = r(x, x2)
+        assert np.all(np.isfinite(y0)), "%s: the unscaled run is not finite" % label
+        for e in (s, -s):
+            xs = np.ldexp(x.view(x.real.dtype), e).view(x.dtype)
+            want = np.ldexp(y0.view(y0.real.dtype), e * degree).view(y0.dtype)
+            tiny = np.finfo(y0.real.dtype).tiny
+            v = np.abs(want.view(y0.real.dtype))
+            assert np.all((v == 0) | (v >= tiny)) and np.all(np.isfinite(v)), "%s: the scaled result leaves the normal range" % label
+            y1 = r(xs, x2)
+            bad = _differing_rows(want, y1)
+            if bad.size:
+                i = int(bad[0])
+                k = int(np.flatnonzero(want[i] != y1[i])[0]) if np.any(want[i] != y1[i]) else 0
+                raise AccuracyError("%s: execute(2^%d x) differs from 2^%d execute(x) in %d rows: %s; row %d bin %d: %r, expected %r"
+                                    % (label, e, e * degree, bad.size, [int(b) for b in bad[:12]], i, k, y1[i, k], want[i, k]))
+    finally:
+        r.free()
+    return y0
+
+
+def check_zeros(run, x, w_out=None, dtype_out=None, x2=None, rows_out=None, label=""):
+    """An all-zero batch (of the shape of x, and of x2) returns zeros of either sign and no NaN."""
+    x = np.ascontiguousarray(x)
+    w_out, dtype_out = w_out or x.shape[1], np.dtype(dtype_out or x.dtype)
+    rows_out = rows_out or x.shape[0]
+    r = _Runs(run, x, w_out, dtype_out, rows_out, x2, label)
+    try:
+        y = r(np.zeros_like(x), None if x2 is None else np.zeros_like(x2))
+    finally:
+        r.free()
+    bad = np.flatnonzero(np.any(~(y == 0), axis=1))
+    if bad.size:
+        i = int(bad[0])
+        k = int(np.flatnonzero(~(y[i] == 0))[0])
+        raise AccuracyError("%s: zeros in, but %d result rows are not zero: %s; row %d bin %d = %r"
+                            % (label, bad.size, [int(b) for b in bad[:12]], i, k, y[i, k]))

@@ -149,6 +149,10 @@ static int run(const void* in, void* out, int n, int batch, int dir, int algo, i
         plan.core.chain_min_log2n = 0;  // the emulated sizes are small: every plan whose tiles agree chains
         if (info) {
             info[0] = 10 + (int)plan.core.passes.size();
+            for (size_t i = 0; i < plan.core.passes.size() && i < 1; i++) {  // the core's first pass: its tile, as for a power of two
+                info[1] = plan.core.passes[i].log2L;
+                info[2] = plan.core.passes[i].log2C;
+            }
             info[4] = (plan.core.hook_capable() && !plan.no_fusion) ? 1 : 0;  // element-wise steps fused into the FFT passes
             if (info[4] && !plan.no_chain && plan.core.chain_capable()) info[4] = 2;  // ... and forward-last + inverse-first as one kernel
             if (info[4] && !plan.no_chain && plan.core.round_capable()) info[4] = 3;  // single pass: FFT -> product -> inverse FFT as ONE kernel

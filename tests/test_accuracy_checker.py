@@ -423,3 +423,117 @@ def test_row_errors_scaled_by_the_larger_of_rms_and_bin():
     assert np.isinf(A.row_errors(y, X, scale="rms_or_bin")[0][0])
     with pytest.raises(ValueError):
         A.row_errors(y, X, scale="max")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the operator checks (tests/operator_ladder.py, accuracy.check_neighbours / check_scaling / check_zeros) see what random rows cannot
+# ---------------------------------------------------------------------------------------------------------------------------
+import operator_ladder as OL  # noqa: E402
+
+
+class DefectPlan(NumpyPlan):
+    """A numpy plan with one defect of the kind only the operator checks see."""
+
+    def __init__(self, n, batch, direction, dtype, defect=None, j0=0, k0=0, delta=0.0):
+        super().__init__(n, batch, direction, dtype, defect)
+        self.j0, self.k0, self.delta = j0, k0, delta
+
+    def execute_ptr(self, d_in, d_out):
+        mem = A.memory()
+        x = mem.d2h(d_in, (self.batch, self.n), self.dtype)
+        with np.errstate(all="ignore"):
+            y = (np.fft.fft(x, axis=1) if self.direction < 0 else np.fft.ifft(x, axis=1)).astype(self.dtype)
+            if self.defect == "matrix_element":    # element (j0, k0) of the matrix is off by delta
+                y[:, self.k0] += self.dtype.type(self.delta) * x[:, self.j0]
+            elif self.defect == "zero_multiply":   # row b gets 0 * (row b + 1): a multiply where a select belongs
+                y[:-1] += self.dtype.type(0) * x[1:]
+            elif self.defect == "flush":
+                y[np.abs(y) < 1e-30] = 0
+            elif self.defect == "unscaled_row":    # the inverse forgets 1/n on one row
+                y[self.j0] *= self.n
+        mem.h2d(d_out, y)
+
+
+def _run_of(plan):
+    return lambda i, _, o: plan.execute_ptr(i, o)
+
+
+def test_perturbed_matrix_element_passes_random_rows_and_fails_the_impulse(host_memory):
+    """The gap: an element of the DFT matrix off by 4 x the bound reaches a random row as 4 x bound / sqrt(n) of its RMS."""
+    n, dt, j0, k0 = 4096, np.complex64, 1234, 77
+    delta = 4 * A.bound("multipass", dt, n)
+    x = A.normal_rows(n, 0, 16, dt, seed=5)
+    A.check_execute(DefectPlan(n, 16, -1, dt, "matrix_element", j0, k0, delta), x, "multipass", label="perturbed, random rows")
+    js = OL.positions(n)
+    imp = OL.impulses(n, js, dt)
+    A.check_execute(NumpyPlan(n, len(js), -1, dt), imp, "multipass", ref=OL.ref_1d(n, -1), kind="impulse", label="numpy, impulses")
+    with pytest.raises(A.AccuracyError, match="1 of 4096 transforms over the bound.*worst transform %d \\(bin %d" % (j0, k0)):
+        A.check_execute(DefectPlan(n, len(js), -1, dt, "matrix_element", j0, k0, delta), imp, "multipass", ref=OL.ref_1d(n, -1),
+                        kind="impulse", label="perturbed, impulses")
+
+
+def test_zero_multiply_leak_passes_every_check_but_the_poisoned_neighbour(host_memory):
+    n, batch, dt = 256, 9, np.complex64
+    x = A.normal_rows(n, 0, batch, dt, seed=6)
+    leak = DefectPlan(n, batch, -1, dt, "zero_multiply")
+    A.check_execute(leak, x, "multipass", label="leak, random rows")
+    A.check_scaling(_run_of(leak), x, label="leak")
+    A.check_zeros(_run_of(leak), x, label="leak")
+    for poison in A.POISONS:
+        A.check_neighbours(_run_of(NumpyPlan(n, batch, -1, dt)), x, [0, 4, 8], poison, label="numpy")
+    with pytest.raises(A.AccuracyError, match="2 untouched result rows changed with their neighbour: rows \\[3, 7\\]"):
+        A.check_neighbours(_run_of(leak), x, [0, 4, 8], "nan", label="leak")
+    with pytest.raises(A.AccuracyError, match="rows \\[3, 7\\]"):
+        A.check_neighbours(_run_of(leak), x, [0, 4, 8], "inf0", label="leak")
+    A.check_neighbours(_run_of(leak), x, [0, 4, 8], "huge", label="leak")  # 0 * a finite value is still 0
+
+
+def test_all_nan_transform_must_come_back_non_finite(host_memory):
+    n, batch, dt = 64, 5, np.complex128
+
+    class Drops(NumpyPlan):
+        def execute_ptr(self, d_in, d_out):
+            mem = A.memory()
+            x = mem.d2h(d_in, (self.batch, self.n), self.dtype)
+            y = np.fft.fft(np.nan_to_num(x), axis=1)
+            mem.h2d(d_out, y)
+
+    x = A.normal_rows(n, 0, batch, dt, seed=7)
+    with pytest.raises(A.AccuracyError, match="result row 2 of an all-NaN transform has 64 finite bins"):
+        A.check_neighbours(_run_of(Drops(n, batch, -1, dt)), x, [2], "nan")
+
+
+def test_flush_to_zero_fails_the_scaling_property(host_memory):
+    n, batch, dt = 256, 5, np.complex128
+    x = A.normal_rows(n, 0, batch, dt, seed=8)
+    A.check_scaling(_run_of(NumpyPlan(n, batch, -1, dt)), x, label="numpy")
+    A.check_execute(DefectPlan(n, batch, -1, dt, "flush"), x, "multipass", label="flush, random rows")
+    with pytest.raises(A.AccuracyError, match="execute\\(2\\^-200 x\\) differs from 2\\^-200 execute\\(x\\) in 5 rows"):
+        A.check_scaling(_run_of(DefectPlan(n, batch, -1, dt, "flush")), x, label="flush")
+
+
+def test_unscaled_inverse_row_fails_the_impulse_check(host_memory):
+    n, dt = 256, np.complex128
+    js = OL.positions(n)
+    imp = OL.impulses(n, js, dt)
+    OL.closed_form_checked(OL.ref_1d(n, 1), OL.ref_1d(n, 1, np.longdouble), imp, "multipass", dt, n)
+    A.check_execute(NumpyPlan(n, n, 1, dt), imp, "multipass", ref=OL.ref_1d(n, 1), kind="impulse", label="numpy inverse")
+    with pytest.raises(A.AccuracyError, match="1 of 256 transforms over the bound.*worst transform 99 "):
+        A.check_execute(DefectPlan(n, n, 1, dt, "unscaled_row", j0=99), imp, "multipass", ref=OL.ref_1d(n, 1), kind="impulse")
+
+
+def test_positions_and_closed_form():
+    assert np.array_equal(OL.positions(4096), np.arange(4096))
+    js = OL.positions(1 << 20)
+    assert {0, 1, (1 << 20) - 1, 1 << 19, 1 << 7, (1 << 7) - 1, (1 << 20) - (1 << 7)} <= set(js.tolist()) and len(js) <= 75
+    assert len(OL.positions(1 << 21)) == len({0, 1} | {x for t in range(22) for x in ((1 << t) % (1 << 21), (1 << t) - 1, (1 << 21) - (1 << t))} - {1 << 21})
+    assert {4200 // 56, 4200 // 56 - 1} <= set(OL.positions(4200, [75, 56]).tolist())
+    for n in (2, 3, 8, 30, 1009, 4096):  # the closed form against numpy's FFT of the impulses, both directions, and c2r / 2D
+        imp = OL.impulses(n, np.arange(n), np.complex128)
+        for d in (-1, 1):
+            ref = np.fft.fft(imp, axis=1) if d < 0 else np.fft.ifft(imp, axis=1)
+            assert np.max(np.abs(OL.ref_1d(n, d)(imp) - ref)) * (1 if d < 0 else n) < 1e-12
+        half = OL.impulses(n // 2 + 1, np.arange(n // 2 + 1), np.complex128)
+        assert np.max(np.abs(OL.ref_c2r(n)(half) - np.fft.irfft(half, n, axis=1))) * n < 1e-12
+    imp = OL.impulses(12 * 32, np.arange(12 * 32), np.complex128)
+    assert np.max(np.abs(OL.ref_2d(12, 32, -1)(imp) - np.fft.fft2(imp.reshape(-1, 12, 32)).reshape(384, -1))) < 1e-12
