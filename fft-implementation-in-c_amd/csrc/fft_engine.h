@@ -97,6 +97,10 @@ struct ExecHooks {
     long long signal_pitch = 0;
     T* power_out = nullptr;
     T power_scale = (T)1;
+    // execute_frames only: `in` holds REAL samples (in_pitch = the hop and signal_pitch count reals), the plan's n is HALF the frame
+    // length, pre_tab the window packed in pairs (HOOK_MUL_PAIR), post_tab = W_2n^k (k < n, shared), and the rows that leave are the
+    // n + 1 one-sided bins of the real transform: complex at out_pitch = n + 1, or power rows of n + 1 reals (TileHooks, HOOK bit 6)
+    bool real_frames = false;
 };
 
 enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6, ALGO_MIXED_RADIX = 7 };
@@ -1283,7 +1287,7 @@ class Pow2Plan {
         }
         if (h.frames_per_signal > 0) {  // overlapping frames (execute_frames): the hooked single-pass rows kernel with its framed load
             if (hook_kind(p) != 1 || side != 3) return;
-            const long long hop = h.in_pitch ? h.in_pitch : n;
+            const long long hop = h.in_pitch ? h.in_pitch : (h.real_frames ? 2 * n : n);
             k.frames_per_signal = h.frames_per_signal;
             k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
             k.signal_pitch = h.signal_pitch;
@@ -1292,6 +1296,15 @@ class Pow2Plan {
             if (((uintptr_t)out & 15) != 0) k.out_vec_ok = 0;
             // a sample belongs to n / hop frames: the loads of overlapping frames carry no non-temporal hint (their lines are asked for again)
             if (hop < n) tp.nt &= ~1;
+            if (h.real_frames) {  // hop, pitch and frame length (2 n) in REAL samples, 16 / sizeof(T) = 2 V of them per 16 bytes
+                k.in_vec_ok = ((hop % (2 * V)) == 0 && (h.signal_pitch % (2 * V)) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+                if (hop < 2 * n) tp.nt &= ~1;
+                k.power_out = h.power_out;
+                k.power_scale = h.power_scale;
+                if (h.power_out) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 32 | 64>, tp, -1, p);
+                else launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 64>, tp, -1, p);
+                return;
+            }
             if (h.power_out) {
                 k.power_out = h.power_out;
                 k.power_scale = h.power_scale;
@@ -1303,7 +1316,7 @@ class Pow2Plan {
         }
         switch (hook_kind(p)) {
             // HOOK bits: 1 load side, 2 store side, 4 table values prefetched with the data, 8 round trip, 16 framed load, 32 one-sided
-            // power store (fft_kernels.h)
+            // power store, 64 real frames (fft_kernels.h)
             case 1: launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3>, tp, -1, p); break;
             case 2: launch_kernel(tile_fft_kernel<T, 8, 1, FAM_R4, LOAD_CCONTIG, STORE_CCONTIG, true, 0, 1 | 4>, tp, -1, p); break;
             case 3: launch_hooked_fixed<FAM_SR16, LOAD_LCONTIG, STORE_CCONTIG, false, 2>(tp, p); break;
@@ -1326,7 +1339,8 @@ class Pow2Plan {
 
     // ---- single-pass sizes: the nf transforms of one launch are overlapping frames of signals (ExecHooks::frames_per_signal,
     // signal_pitch; in_pitch = the hop), windowed by h.pre_tab on the way in; the results leave as complex rows of n bins (out) or,
-    // with h.power_out, as one-sided power rows.  Requires round_capable() and frames_exact(nf, frames_per_signal).
+    // with h.power_out, as one-sided power rows.  h.real_frames: the signals are real, a frame is 2 n reals and n + 1 bins leave.
+    // Requires round_capable() and frames_exact(nf, frames_per_signal).
     // The frame -> (signal, frame in signal) split in the kernel is one multiply-high by ceil(2^32 / d): exact while f * d < 2^32
     // for every tile column f, the padding columns of the last tile included.
     bool frames_exact(long long nf, int frames_per_signal) const {

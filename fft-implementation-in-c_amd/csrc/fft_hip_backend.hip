@@ -887,10 +887,10 @@ int fft_gpu_execute_fused_hip(fft_gpu_plan_t p, const void* d_x, const void* d_y
 }
 
 // STFT / spectrogram / Welch PSD on overlapping frames (fft_plans_ext.h FramesPlan); w_host: the n window values of
-// FFT_GPU_WINDOW_USER (host memory, reals of `prec`), ignored otherwise
-fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
-                                       fft_gpu_frames_out_t out, fft_precision_t prec) {
-    if (n < 2 || (n & (n - 1)) != 0 || hop < 1 || hop > n || signal_len < n || n_signals < 1 || (int)window < 0 || (int)window > 4 ||
+// FFT_GPU_WINDOW_USER (host memory, reals of `prec`), ignored otherwise.  real_input: real signals, one-sided rows, n >= 4
+static fft_gpu_plan_t plan_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                  fft_gpu_frames_out_t out, fft_precision_t prec, bool real_input) {
+    if (n < (real_input ? 4 : 2) || (n & (n - 1)) != 0 || hop < 1 || hop > n || signal_len < n || n_signals < 1 || (int)window < 0 || (int)window > 4 ||
         (window == FFT_GPU_WINDOW_USER && !w_host) || (int)out < 0 || (int)out > 2 ||
         (long long)n_signals * ((signal_len - (n - hop)) / hop) > 0x7fffffff) {
         fprintf(stderr, "fft_hip: invalid frames plan arguments (n=%d hop=%d signal_len=%d signals=%d window=%d out=%d)\n", n, hop, signal_len,
@@ -903,12 +903,20 @@ fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_sig
     bool ok;
     if (prec == FFT_PREC_F32) {
         p->w32 = new (std::nothrow) ffteng::FramesPlan<float, HipRT>();
-        ok = p->w32 && p->w32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out);
+        ok = p->w32 && p->w32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out, real_input);
     } else {
         p->w64 = new (std::nothrow) ffteng::FramesPlan<double, HipRT>();
-        ok = p->w64 && p->w64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out);
+        ok = p->w64 && p->w64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out, real_input);
     }
-    return finish_plan(p, ok, "frames");
+    return finish_plan(p, ok, real_input ? "real frames" : "frames");
+}
+fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                       fft_gpu_frames_out_t out, fft_precision_t prec) {
+    return plan_frames(n, hop, signal_len, n_signals, window, w_host, out, prec, false);
+}
+fft_gpu_plan_t fft_gpu_plan_frames_real_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                            fft_gpu_frames_out_t out, fft_precision_t prec) {
+    return plan_frames(n, hop, signal_len, n_signals, window, w_host, out, prec, true);
 }
 // frames per signal: nw = (signal_len - (n - hop)) / hop
 int fft_gpu_frames_count_hip(fft_gpu_plan_t p) {
@@ -917,7 +925,8 @@ int fft_gpu_frames_count_hip(fft_gpu_plan_t p) {
     if (p->w64) return p->w64->nw;
     return -1;
 }
-// async on the plan's stream.  d_x: the signals, signal_pitch elements apart (0: signal_len); d_out: see fft_gpu_frames_out_t
+// async on the plan's stream.  d_x: the signals, signal_pitch elements apart (0: signal_len; reals for a real frames plan, which
+// reads d_x as such); d_out: see fft_gpu_frames_out_t
 int fft_gpu_execute_frames_hip(fft_gpu_plan_t p, const void* d_x, long long signal_pitch, void* d_out, double sample_rate) {
     if (!p || !d_x || !d_out || d_x == d_out || (!p->w32 && !p->w64)) return -1;
     DeviceGuard guard(p->device);
@@ -1317,6 +1326,8 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         info->fused = w->fused() ? 1 : 0;
         if (w->power) info->workspace_bytes += (size_t)w->frames() * (size_t)w->bins() * sizeof(*w->power);
         if (w->work) info->workspace_bytes += (size_t)w->frames() * (size_t)w->n * sizeof(*w->work);
+        if (w->zwork) info->workspace_bytes += (size_t)w->frames() * (size_t)(w->n / 2) * sizeof(*w->zwork);
+        if (w->xwork) info->workspace_bytes += (size_t)w->frames() * (size_t)w->bins() * sizeof(*w->xwork);
     };
     if (p->w32) fill_frames(p->w32);
     if (p->w64) fill_frames(p->w64);

@@ -68,7 +68,9 @@ enum { FAM_SR16 = 0, FAM_R4 = 1, FAM_R2 = 2 };
 //   store: out[idx] = X[idx] (* post_tab[b * post_tab_b + idx] | * conj(...) | -> |X[idx]|^2), only for idx < n_out
 // Different row pitches of the user's arrays (Bluestein: n on the outside, m inside) are the ordinary in_b / out_b
 // (in_c / out_c for the single-pass kernel) of TileParams, set by the launcher.
-enum { HOOK_NONE = 0, HOOK_MUL = 1, HOOK_MUL_CONJ = 2, HOOK_ABS2 = 3 };
+// HOOK_MUL_PAIR (load side of the real-frames kernel only): the table entry is a PAIR of real factors, applied component by component
+// (re *= w.re, im *= w.im) -- not a complex product.
+enum { HOOK_NONE = 0, HOOK_MUL = 1, HOOK_MUL_CONJ = 2, HOOK_ABS2 = 3, HOOK_MUL_PAIR = 4 };
 template <typename T>
 struct TileHooks {
     const cpx<T>* pre_tab;
@@ -96,6 +98,15 @@ struct TileHooks {
     // applications/power_spectrum.c:75-80).  Rows of L/2 + 1 values start only sizeof(T)-aligned: scalar stores.
     T* power_out;
     T power_scale;
+    // HOOK bit 6 (single-pass kernel only, with bits 0, 1 and 4): REAL FRAMES.  `in` is an array of REAL samples and frame f starts at
+    // real sample (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_c of it (hop and pitch count reals).  A
+    // frame of n = 2 L reals is loaded as the L complex values z[m] = y[2m] + i y[2m+1] (the reals read as pairs; pre_mode =
+    // HOOK_MUL_PAIR, pre_tab[m] = (w[2m], w[2m+1]), n_in = L) and the store side splits the length-L spectrum Z into the
+    // L + 1 non-redundant bins of the length-n real transform (Z[L] = Z[0]):
+    //   E = (Z[k] + conj Z[L-k]) / 2,  O = (Z[k] - conj Z[L-k]) / (2i),  X[k] = E + W_n^k O,  W_n^k = post_tab[k], k < L
+    //   X[0] = Re Z[0] + Im Z[0],  X[L] = Re Z[0] - Im Z[0]   (imaginary parts exactly 0)
+    // Rows of L + 1 bins: complex at out + f * out_c, or with bit 5 one-sided power rows at power_out + f * (L + 1)
+    // (|X[k]|^2 * power_scale, doubled for 0 < k < L).  Rows start only sizeof(cpx<T>)- / sizeof(T)-aligned: per-value stores.
 };
 
 template <typename T>
@@ -482,8 +493,9 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 // HOOK: 0 none; bit 0 the load side of TileHooks is compiled in, bit 1 the store side, bit 2 the load-side table values
 // are prefetched together with the data (+ E * 4 VGPRs per group: the 2-waves-per-SIMD kernels; without it they are read
 // when the data is consumed -- the 4-waves-per-SIMD rows kernel, whose 128-VGPR budget has no room for them), bit 3 FFT ->
-// product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store (TileHooks; the last three on the
-// hooked single-pass rows kernel only).  Compile-time bits: an instantiation without one compiles to the code it had before.
+// product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store, bit 6 real frames: packed real load and
+// the r2c split in the store (TileHooks; the last four on the hooked single-pass rows kernel only, bit 6 only with bits 0, 1
+// and 4).  Compile-time bits: an instantiation without one compiles to the code it had before.
 // waves per SIMD the register budget of an instantiation is sized for.  The fp32 kernels with their shape baked in need only
 // 92-122 VGPRs when built for four waves per SIMD (no spills; built for two they take 150-250 because they may), i.e. two
 // 512-thread workgroups per CU.  Measured (profiles/r2_ab_rows_fixed.txt): the single-pass rows kernel gains 5...12 % from
@@ -556,8 +568,10 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
     vec16<T> nxtbuf[DEPTH][H][E];
     constexpr bool HK_LOAD = (HOOK & 1) != 0, HK_STORE = (HOOK & 2) != 0, HK_TABPF = (HOOK & 4) != 0, HK_ROUND = (HOOK & 8) != 0;
     constexpr bool HK_FRAMES = (HOOK & 16) != 0, HK_POWER = (HOOK & 32) != 0;  // TileHooks: framed load, one-sided power store
-    static_assert(!(HK_FRAMES || HK_POWER) || (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && HK_LOAD && HK_STORE),
+    constexpr bool HK_REAL = (HOOK & 64) != 0;  // TileHooks: real frames (packed real load, r2c split in the store)
+    static_assert(!(HK_FRAMES || HK_POWER || HK_REAL) || (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && HK_LOAD && HK_STORE),
                   "frames / power hooks: the hooked single-pass rows kernel only");
+    static_assert(!HK_REAL || (HK_FRAMES && !HK_TABPF && !HK_ROUND && H == 1), "real frames: with the framed load on the hooked single-pass rows kernel only");
     vec16<T> nxttab[HK_TABPF ? DEPTH : 1][HK_TABPF ? H : 1][HK_TABPF ? E : 1];  // the load-side table values of the same chunks
     const bool pre_on = HK_LOAD && p.hk.pre_mode != HOOK_NONE;  // wave-uniform
     // index (inside its transform) of the first sample of lane-load i of group h, and its tile column / row
@@ -581,6 +595,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
             for (int i = 0; i < E; i++) {
                 bool live;
                 const cpx<T>* src;
+                const T* rsrc = nullptr;  // HK_REAL: the chunk's first real sample (an address that may be only sizeof(T)-aligned)
                 if (LOADM == LOAD_CCONTIG) {
                     const long long l = r + ((long long)i << log2TPC);
                     live = (tc.c0 + h * CG + V * j) < p.n_cols;
@@ -595,7 +610,12 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     if (HK_FRAMES) {  // frame f of the execute: signal f / frames_per_signal, frame f % frames_per_signal inside it
                         const unsigned f = (unsigned)(tc.c0 + t), fps = (unsigned)p.hk.frames_per_signal;
                         const unsigned sig = fps == 1u ? f : (unsigned)(((unsigned long long)f * p.hk.frames_rcp) >> 32);
-                        src = p.in + (long long)sig * p.hk.signal_pitch + (long long)(f - sig * fps) * p.in_c + l0;
+                        if (HK_REAL) {  // hop and pitch count REAL samples; sample pair l0 of the frame is its reals 2 l0, 2 l0 + 1
+                            rsrc = reinterpret_cast<const T*>(p.in) + (long long)sig * p.hk.signal_pitch + (long long)(f - sig * fps) * p.in_c + 2 * l0;
+                            src = nullptr;
+                        } else {
+                            src = p.in + (long long)sig * p.hk.signal_pitch + (long long)(f - sig * fps) * p.in_c + l0;
+                        }
                     }
                 }
                 if (HK_LOAD) {
@@ -606,7 +626,16 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     FFT_UNROLL
                     for (int vv = 0; vv < V; vv++) nxt[h][i].c[vv] = mk<T>((T)0, (T)0);
                     if (live && idx0 < n_in) {
-                        if (p.hk.in_vec_ok && idx0 + V <= n_in) {
+                        if (HK_REAL) {
+                            // in_vec_ok: every frame starts 16-byte aligned (base, hop and pitch), so does every chunk of it.  Otherwise
+                            // component by component: no cpx<T> is read at an address that is not sizeof(cpx<T>)-aligned (odd hop)
+                            if (p.hk.in_vec_ok) {
+                                nxt[h][i] = fft_ld16<NTL>(reinterpret_cast<const vec16<T>*>(rsrc));
+                            } else {
+                                FFT_UNROLL
+                                for (int vv = 0; vv < V; vv++) nxt[h][i].c[vv] = mk<T>(rsrc[2 * vv], rsrc[2 * vv + 1]);
+                            }
+                        } else if (p.hk.in_vec_ok && idx0 + V <= n_in) {
                             nxt[h][i] = fft_ld16<NTL>(reinterpret_cast<const vec16<T>*>(src));
                         } else {
                             FFT_UNROLL
@@ -643,7 +672,8 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                 for (int vv = 0; vv < V; vv++) {
                     if (idx0 + vv < p.hk.n_in) {
                         const cpx<T> w = tv.c[vv];
-                        nxt[h][i].c[vv] = p.hk.pre_mode == HOOK_MUL_CONJ ? cmul_conj(nxt[h][i].c[vv], w) : cmul(nxt[h][i].c[vv], w);
+                        if (HK_REAL) nxt[h][i].c[vv] = mk<T>(nxt[h][i].c[vv].re * w.re, nxt[h][i].c[vv].im * w.im);  // HOOK_MUL_PAIR: two real window values
+                        else nxt[h][i].c[vv] = p.hk.pre_mode == HOOK_MUL_CONJ ? cmul_conj(nxt[h][i].c[vv], w) : cmul(nxt[h][i].c[vv], w);
                     }
                 }
             }
@@ -897,7 +927,43 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                         const int g = tid + i * nthreads;
                         const int t = h * CG + (g >> log2CPR);
                         const int pos = g & cpr_mask;
-                        if (HK_POWER) {  // one-sided power of frame c0 + t: bins pos * V ... that are <= L/2, every store predicated
+                        if (HK_REAL) {
+                            // r2c split of frame c0 + t (TileHooks, bit 6): bins k = pos * V ... of its L + 1.  Z[k] is this thread's own chunk,
+                            // Z[L - k] lies in the SAME LDS row, complete since the barrier above: no new barrier.  The pos == 0 thread also
+                            // writes bin L.  Columns at or past n_cols -- the ragged last tile's, and a short batch's padding -- were loaded as
+                            // zeros without touching memory and write nothing: every store below sits under this one predicate.
+                            if (tc.c0 + t < p.n_cols) {
+                                const unsigned char* zrow = smem + h * group_bytes + (size_t)(g >> log2CPR) * pitch;
+                                const vec16<T> v = *reinterpret_cast<const vec16<T>*>(zrow + (size_t)pos * 16);
+                                const long long f = tc.c0 + t;
+                                cpx<T>* crow = tc.out + (long long)t * p.out_c;
+                                T* prow = HK_POWER ? p.hk.power_out + f * (L + 1) : nullptr;
+                                auto put = [&](int k, cpx<T> X) __attribute__((always_inline)) {
+                                    if (HK_POWER) {
+                                        T pw = (X.re * X.re + X.im * X.im) * p.hk.power_scale;
+                                        if (k > 0 && k < L) pw *= (T)2;
+                                        prow[k] = pw;
+                                    } else {
+                                        crow[k] = X;
+                                    }
+                                };
+                                FFT_UNROLL
+                                for (int vv = 0; vv < V; vv++) {
+                                    const int k = pos * V + vv;
+                                    const cpx<T> a = v.c[vv];
+                                    if (k == 0) {
+                                        put(0, mk<T>(a.re + a.im, (T)0));
+                                        put(L, mk<T>(a.re - a.im, (T)0));
+                                    } else {
+                                        const cpx<T> m = *reinterpret_cast<const cpx<T>*>(zrow + (size_t)(L - k) * SZ);
+                                        const cpx<T> c = mk<T>(m.re, -m.im);                     // conj Z[L-k]
+                                        const cpx<T> e = cscale(cadd(a, c), (T)0.5);
+                                        const cpx<T> o = mul_neg_i(cscale(csub(a, c), (T)0.5));  // (a - c) / (2i)
+                                        put(k, cadd(e, cmul(p.hk.post_tab[k], o)));
+                                    }
+                                }
+                            }
+                        } else if (HK_POWER) {  // one-sided power of frame c0 + t: bins pos * V ... that are <= L/2, every store predicated
                             const int half = L >> 1;
                             if (tc.c0 + t < p.n_cols && pos * V <= half) {
                                 const vec16<T> v = *reinterpret_cast<const vec16<T>*>(smem + h * group_bytes + (size_t)(g >> log2CPR) * pitch + (size_t)pos * 16);

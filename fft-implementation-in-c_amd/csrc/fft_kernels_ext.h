@@ -145,6 +145,39 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) psd_onesided_kernel(const cpx<T>* X, T* p
     }
 }
 
+// The same for rows that already hold only their one-sided bins (the r2c split's rows of hb = n/2 + 1 bins, `pitch` elements apart):
+// psd[b][k] = |X[b][k]|^2 * scale, doubled for 0 < k < hb - 1.  `total` = batch * hb.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) psd_onesided_rows_kernel(const cpx<T>* X, long long pitch, T* psd, int hb, T scale, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long b = i / hb;
+        const int k = (int)(i - b * hb);
+        const cpx<T> v = X[b * pitch + k];
+        T pw = (v.re * v.re + v.im * v.im) * scale;
+        if (k > 0 && k < hb - 1) pw *= (T)2;
+        psd[i] = pw;
+    }
+}
+
+// Real frames -> the packed complex rows a half-length transform reads (the unfused path of the real frames plan):
+// z[f][m] = (x_f[2m] * win[m].re, x_f[2m+1] * win[m].im), m < h, where frame f = s * nw + w starts at real sample
+// s * signal_pitch + w * hop of x and win[m] = (w[2m], w[2m+1]).  Read value by value: a frame may start at any real.
+// `total` = frames * h.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_pack_real_kernel(const T* x, long long signal_pitch, int hop, int nw, int h, const cpx<T>* win, cpx<T>* z,
+                                                                long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long f = i / h;
+        const int m = (int)(i - f * h);
+        const long long s = f / nw;
+        const T* src = x + s * signal_pitch + (f - s * nw) * (long long)hop + 2 * m;
+        const cpx<T> w = win[m];
+        z[i] = mk<T>(src[0] * w.re, src[1] * w.im);
+    }
+}
+
 // Welch average of periodograms: psd[s][k] = (1 / nw) * sum_w power[s][w][k], power: [signals][nw][hb] one-sided power rows
 // (hb = n/2 + 1), psd: [signals][hb].  One thread per output value, lanes along k (coalesced on both sides); w ascends inside the
 // thread and the sum is kept in double for both precisions (the kernel is memory bound, and the error must not grow with the

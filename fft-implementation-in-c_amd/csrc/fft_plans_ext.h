@@ -397,6 +397,15 @@ class FusedPlan {
 // frames_mean_kernel.  Every other n, and no_fusion: per signal one execute_hooked with in_pitch = hop (pad_mul_kernel + a plain
 // execute where the core has no hooks or a signal does not start 16-byte aligned), psd_onesided_kernel, frames_mean_kernel --
 // a correct fallback, not a tuned one.
+//
+// real_input: x holds REAL signals (signal_len, hop, signal_pitch count reals), n a power of two >= 4, and every row is one-sided:
+//   FRAMES_STFT out[s][w][k], k <= n/2 complex; POWER / WELCH as above.  The core is the transform of HALF the length, L = n/2, on
+//   z[m] = y[2m] + i y[2m+1] (y the windowed frame: the reals read as complex pairs, the window table packed the same way), and
+//   the split  E = (Z[k] + conj Z[L-k]) / 2, O = (Z[k] - conj Z[L-k]) / (2i), X[k] = E + W_n^k O  yields the n/2 + 1 bins.
+//   Where L fits one hook-capable pass the split rides in that pass's store (tile_fft_kernel HOOK bit 6: both Z[k] and Z[L-k] of a
+//   frame lie in one LDS row there): one launch reads the reals in place and writes the one-sided rows.  Every other n, and
+//   no_fusion: frames_pack_real_kernel (windowed frames -> [frames][L] complex), the plain core, r2c_split_kernel, and for POWER /
+//   WELCH psd_onesided_rows_kernel -- correct, not tuned.
 // ---------------------------------------------------------------------------
 enum FramesWindow { WINDOW_RECT = 0, WINDOW_HANN = 1, WINDOW_HAMMING = 2, WINDOW_BLACKMAN = 3, WINDOW_USER = 4 };
 enum FramesOut { FRAMES_STFT = 0, FRAMES_POWER = 1, FRAMES_WELCH = 2 };
@@ -413,26 +422,31 @@ class FramesPlan {
     cpx<T>* win = nullptr;    // the window as complex values, + 1 padding entry (ExecHooks::pre_tab)
     T* power = nullptr;       // WELCH: [n_signals * nw][n/2 + 1]
     cpx<T>* work = nullptr;   // fallback, POWER / WELCH: the complex rows [n_signals * nw][n] (allocated at its first use)
+    bool real_input = false;  // real signals, one-sided rows (see above); win then holds n/2 (+ 1) PAIRS of window values
+    cpx<T>* wsplit = nullptr; // real_input: W_n^k, k <= n/2
+    cpx<T>* zwork = nullptr;  // real_input fallback: the packed frames and their spectra [n_signals * nw][n/2] (allocated at its first use)
+    cpx<T>* xwork = nullptr;  // real_input fallback, POWER / WELCH: the split rows [n_signals * nw][n/2 + 1] (allocated at its first use)
     bool ok = false;
     bool no_fusion = false;
     ~FramesPlan() {
         if (!rt) return;
-        rt->dfree(win); rt->dfree(power); rt->dfree(work);
+        rt->dfree(win); rt->dfree(power); rt->dfree(work); rt->dfree(wsplit); rt->dfree(zwork); rt->dfree(xwork);
     }
     long long frames() const { return (long long)n_signals * nw; }
     int bins() const { return n / 2 + 1; }
     bool fused() const { return ok && !no_fusion && core.round_capable() && core.frames_exact(frames(), nw); }
 
     // w_host: n window values of type T (WINDOW_USER), ignored otherwise
-    bool build(RT* runtime, int n_, int hop_, int signal_len_, int n_signals_, int window_, const T* w_host, int out_kind_) {
+    bool build(RT* runtime, int n_, int hop_, int signal_len_, int n_signals_, int window_, const T* w_host, int out_kind_, bool real_input_ = false) {
         rt = runtime; n = n_; hop = hop_; signal_len = signal_len_; n_signals = n_signals_; window = window_; out_kind = out_kind_;
-        if (n < 2 || (n & (n - 1)) != 0 || n > (1 << 29) || hop < 1 || hop > n || signal_len < n || n_signals < 1) return false;
+        real_input = real_input_;
+        if (n < (real_input ? 4 : 2) || (n & (n - 1)) != 0 || n > (1 << 29) || hop < 1 || hop > n || signal_len < n || n_signals < 1) return false;
         if (window < WINDOW_RECT || window > WINDOW_USER || (window == WINDOW_USER && !w_host)) return false;
         if (out_kind < FRAMES_STFT || out_kind > FRAMES_WELCH) return false;
         nw = (signal_len - (n - hop)) / hop;
         if (nw < 1 || frames() > 0x7fffffff || frames() * (long long)n > (1ll << 40)) return false;
         core.wants_hooks = true;
-        if (!core.build(rt, ilog2(n), ALGO_AUTO, (int)frames())) return false;
+        if (!core.build(rt, ilog2(real_input ? n / 2 : n), ALGO_AUTO, (int)frames())) return false;
         // the reference's windows with their n - 1 denominators (power_spectrum.c:5-25), as complex values; + 1 padding entry
         std::vector<cpx<T>> wv((size_t)n + 1);
         const long double two_pi = 6.283185307179586476925286766559005768L;
@@ -451,6 +465,21 @@ class FramesPlan {
         wv[(size_t)n] = wv[0];
         window_power = window == WINDOW_HANN ? 0.375L * (long double)n : sum2;
         if (out_kind != FRAMES_STFT && !(window_power > 0.0L)) return false;
+        if (real_input) {  // entry m = (w[2m], w[2m+1]): the factors of the real samples that make up complex sample m (+ 1 padding entry)
+            const int h = n / 2;
+            for (int m = 0; m < h; m++) {
+                const T w0 = wv[(size_t)(2 * m)].re, w1 = wv[(size_t)(2 * m + 1)].re;
+                wv[(size_t)m].re = w0;
+                wv[(size_t)m].im = w1;
+            }
+            wv[(size_t)h] = wv[0];
+            wv.resize((size_t)h + 1);
+            std::vector<cpx<T>> t;
+            make_twiddle_table<T>(t, n, (long long)h + 1, 1);
+            wsplit = (cpx<T>*)rt->dmalloc(t.size() * SZ);
+            if (!wsplit) return false;
+            rt->h2d(wsplit, t.data(), t.size() * SZ);
+        }
         win = (cpx<T>*)rt->dmalloc(wv.size() * SZ);
         if (!win) return false;
         rt->h2d(win, wv.data(), wv.size() * SZ);
@@ -463,6 +492,7 @@ class FramesPlan {
     }
 
     // x: the signals (signal_pitch elements apart; 0: signal_len); out: see FramesOut.  0 / -1 (bad arguments: nothing is launched)
+    // real_input: x points at REAL samples and signal_pitch counts reals
     int execute(const cpx<T>* x, long long signal_pitch, void* out, double sample_rate) {
         if (!ok || !x || !out || (const void*)x == (const void*)out) return -1;
         if (signal_pitch == 0) signal_pitch = signal_len;
@@ -471,7 +501,36 @@ class FramesPlan {
         const int hb = bins();
         const T scale = (T)(1.0L / ((long double)sample_rate * window_power));
         T* rows = out_kind == FRAMES_WELCH ? power : (T*)out;  // where the power rows go
-        if (fused()) {
+        if (real_input) {
+            const int h = n / 2;
+            if (fused()) {
+                ExecHooks<T> f;
+                f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL_PAIR;
+                f.n_in = h; f.in_pitch = hop;
+                f.frames_per_signal = nw; f.signal_pitch = signal_pitch;
+                f.real_frames = true; f.post_tab = wsplit; f.out_pitch = hb;
+                if (out_kind == FRAMES_STFT) {
+                    core.execute_frames(x, (cpx<T>*)out, (int)nf, f);
+                } else {
+                    f.power_out = rows; f.power_scale = scale;
+                    core.execute_frames(x, reinterpret_cast<cpx<T>*>(rows), (int)nf, f);  // (complex `out` unused: the power store replaces it)
+                }
+            } else {
+                if (!zwork) zwork = (cpx<T>*)rt->dmalloc((size_t)nf * (size_t)h * SZ);
+                if (!zwork) return -1;
+                cpx<T>* X = (cpx<T>*)out;
+                if (out_kind != FRAMES_STFT) {
+                    if (!xwork) xwork = (cpx<T>*)rt->dmalloc((size_t)nf * (size_t)hb * SZ);
+                    if (!xwork) return -1;
+                    X = xwork;
+                }
+                launch_flat(rt, fftk::frames_pack_real_kernel<T>, nf * h, reinterpret_cast<const T*>(x), signal_pitch, hop, nw, h, (const cpx<T>*)win, zwork, nf * h);
+                core.execute(zwork, zwork, (int)nf, false);
+                launch_flat(rt, fftk::r2c_split_kernel<T>, nf * (h / 2 + 1), (const cpx<T>*)zwork, X, (const cpx<T>*)wsplit, h, nf * (h / 2 + 1));
+                if (out_kind != FRAMES_STFT)
+                    launch_flat(rt, fftk::psd_onesided_rows_kernel<T>, nf * hb, (const cpx<T>*)X, (long long)hb, rows, hb, scale, nf * hb);
+            }
+        } else if (fused()) {
             ExecHooks<T> f;
             f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL;
             f.n_in = n; f.in_pitch = hop;

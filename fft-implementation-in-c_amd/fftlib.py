@@ -67,6 +67,7 @@ SIGNATURES = {
     "fft_gpu_plan_fused_hip": (_vp, [_i, _i, _i, _vp, _i, _i]), "fft_gpu_fused_out_len_hip": (_i, [_vp]),
     "fft_gpu_execute_fused_hip": (_i, [_vp, _vp, _vp, _vp, C.c_double]),
     "fft_gpu_plan_frames_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count_hip": (_i, [_vp]),
+    "fft_gpu_plan_frames_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_execute_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "fft_gpu_dft_1d_f32": (_i, [_vp, _vp, _i, _i]), "fft_gpu_dft_1d_batch_f32": (_i, [_vp, _vp, _i, _i, _i]),
     "fft_gpu_bit_reverse": (_i, [_vp, _vp, _i, _i, _i]),
     "fft_gpu_plan_frames": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count": (_i, [_vp]),
+    "fft_gpu_plan_frames_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_execute_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
@@ -103,7 +105,7 @@ SIGNATURES = {
     "fft_convolution_gpu": (_i, [_vp, _i, _vp, _i, _vp]), "circular_convolution_gpu": (_i, [_vp, _vp, _i, _vp]),
     "compute_periodogram_gpu": (_vp, [_vp, _i, C.c_double]), "autocorrelation_fft_gpu": (_vp, [_vp, _i]),
     "cross_correlation_fft_gpu": (_vp, [_vp, _vp, _i]),
-    "fft_welch_psd_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]),
+    "fft_welch_psd_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]), "fft_welch_psd_real_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -309,22 +311,29 @@ class ExtPlan:
 
     @classmethod
     def frames(cls, n, hop, signal_len, n_signals=1, window="hann", out="stft", dtype=np.complex128):
-        """STFT / spectrogram ("power") / Welch plan on overlapping frames.  window: a name of WINDOWS, or n real values (USER)."""
+        """STFT / spectrogram ("power") / Welch plan on overlapping frames.  window: a name of WINDOWS, or n real values (USER).
+        dtype float32 / float64: the plan for REAL signals (fft_gpu_plan_frames_real_hip), whose rows are one-sided."""
         dt = np.dtype(dtype)
+        real = dt in (np.dtype(np.float32), np.dtype(np.float64))
         w = None
         if not isinstance(window, str):
-            w = np.ascontiguousarray(np.asarray(window).astype(np.float32 if dt == np.complex64 else np.float64))
+            w = np.ascontiguousarray(np.asarray(window).astype(np.float32 if dt in (np.complex64, np.float32) else np.float64))
             if w.shape != (n,):
                 raise ValueError("a user window has n values")
-        p = cls(init().fft_gpu_plan_frames_hip(n, hop, signal_len, n_signals, WINDOWS["user" if w is not None else window],
-                                               None if w is None else w.ctypes.data, FRAMES_OUT[out], _prec_of(dt)))
-        p.n, p.n_signals, p.out, p.dtype = n, n_signals, out, dt
+        lib = init()
+        make = lib.fft_gpu_plan_frames_real_hip if real else lib.fft_gpu_plan_frames_hip
+        prec = (PREC_F32 if dt == np.float32 else PREC_F64) if real else _prec_of(dt)
+        p = cls(make(n, hop, signal_len, n_signals, WINDOWS["user" if w is not None else window],
+                     None if w is None else w.ctypes.data, FRAMES_OUT[out], prec))
+        p.n, p.n_signals, p.out, p.dtype, p.real = n, n_signals, out, dt, real
         p.nw = p.lib.fft_gpu_frames_count_hip(p.handle)
         return p
 
     def frames_out(self):
         """(shape, dtype) of a frames plan's result."""
-        rdt = np.dtype(np.float32 if self.dtype == np.complex64 else np.float64)
+        rdt = np.dtype(np.float32 if self.dtype in (np.complex64, np.float32) else np.float64)
+        if self.out == "stft" and self.real:  # one-sided rows
+            return (self.n_signals, self.nw, self.n // 2 + 1), np.dtype(np.complex64 if rdt == np.float32 else np.complex128)
         if self.out == "stft":
             return (self.n_signals, self.nw, self.n), self.dtype
         if self.out == "power":
@@ -463,7 +472,9 @@ def _frames(x, n, hop, window, out, fs):
 
 def stft(x, n, hop, window="hann"):
     """x: [signals, len] (or [len]) complex -> [signals, frames, n] complex: the transform of every windowed frame
-    x[s, w * hop : w * hop + n], frames = (len - (n - hop)) // hop; window: a name of WINDOWS or n real values."""
+    x[s, w * hop : w * hop + n], frames = (len - (n - hop)) // hop; window: a name of WINDOWS or n real values.
+    A float32 / float64 x (here, in spectrogram and in welch) is read as real signals where it lies -- no complex copy -- and
+    the rows are one-sided: [signals, frames, n//2 + 1]."""
     return _frames(x, n, hop, window, "stft", 1.0)
 
 

@@ -114,3 +114,33 @@ double* fft_welch_psd_gpu(const complex_t* signal, int signal_len, double sample
     }
     return psd;
 }
+
+double* fft_welch_psd_real_gpu(const double* signal, int signal_len, double sample_rate, int window_size, int overlap) {
+    if (!signal || window_size < 4 || !is_power_of_two(window_size) || overlap < 0 || overlap >= window_size || signal_len < window_size) {
+        fprintf(stderr, "Error: real Welch PSD needs a power-of-two window_size >= 4, 0 <= overlap < window_size <= signal_len\n");
+        return NULL;
+    }
+    if (ensure_gpu() != 0) return NULL;
+    const size_t bins = (size_t)window_size / 2 + 1;
+    double* psd = (double*)malloc(bins * sizeof(double));
+    if (!psd) return NULL;
+    int rc = -1;
+    fft_gpu_plan_t plan = fft_gpu_plan_frames_real_hip(window_size, window_size - overlap, signal_len, 1, FFT_GPU_WINDOW_HANN, NULL, FFT_GPU_FRAMES_WELCH,
+                                                       FFT_PREC_F64);
+    fft_gpu_memory_t dx = plan ? fft_gpu_alloc_bytes_hip((size_t)signal_len * sizeof(double)) : NULL;
+    fft_gpu_memory_t dout = plan ? fft_gpu_alloc_bytes_hip(bins * sizeof(double)) : NULL;
+    if (plan && dx && dout) {
+        if (fft_gpu_copy_h2d_bytes_hip(dx, signal, (size_t)signal_len * sizeof(double)) == 0 &&
+            fft_gpu_execute_frames_hip(plan, fft_gpu_memory_ptr(dx), 0, fft_gpu_memory_ptr(dout), sample_rate) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+            fft_gpu_copy_d2h_bytes_hip(psd, dout, bins * sizeof(double)) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(dx);
+    fft_gpu_free(dout);
+    fft_gpu_destroy_plan(plan);
+    if (rc != 0) {
+        free(psd);
+        return NULL;
+    }
+    return psd;
+}

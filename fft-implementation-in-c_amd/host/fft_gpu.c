@@ -193,6 +193,12 @@ fft_gpu_plan_t fft_gpu_plan_frames(int n, int hop, int signal_len, int n_signals
     return fft_gpu_plan_frames_hip(n, hop, signal_len, n_signals, window, w_host, out, prec);
 }
 
+fft_gpu_plan_t fft_gpu_plan_frames_real(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                        fft_gpu_frames_out_t out, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_frames_real")) return NULL;
+    return fft_gpu_plan_frames_real_hip(n, hop, signal_len, n_signals, window, w_host, out, prec);
+}
+
 int fft_gpu_frames_count(fft_gpu_plan_t plan) { return fft_gpu_frames_count_hip(plan); }
 
 int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch, void* d_out, double sample_rate) {

@@ -35,6 +35,9 @@ complex_t* cross_correlation_fft_gpu(const complex_t* x, const complex_t* y, int
  * array of window_size/2 + 1 doubles freed by the caller; NULL on failure.  ONE frames plan (fft_gpu_plan_frames_hip): the windows
  * are read in place on the device, nothing is copied per window. */
 double* fft_welch_psd_gpu(const complex_t* signal, int signal_len, double sample_rate, int window_size, int overlap);
+/* The same for a REAL signal (window_size a power of two >= 4): ONE real frames plan (fft_gpu_plan_frames_real_hip) reads the doubles
+ * in place on the device, no complex copy of the signal is made anywhere. */
+double* fft_welch_psd_real_gpu(const double* signal, int signal_len, double sample_rate, int window_size, int overlap);
 
 #ifdef __cplusplus
 }

@@ -202,8 +202,24 @@ int fft_gpu_execute_fused_hip(fft_gpu_plan_t plan, const void* d_x, const void* 
  * the core's passes, fused = 1 when the framed load and the stores ride on the pass.  Sync, set_stream, destroy as for fused plans. */
 fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window,
                                        const void* w_host /* n reals of prec, USER only */, fft_gpu_frames_out_t out, fft_precision_t prec);
+/* The same for REAL signals, with one-sided rows: n_signals signals of signal_len REAL samples of `prec` (float / double), frame
+ * w of a signal = its reals w * hop ... w * hop + n - 1; n: a power of two >= 4 (n = 2 returns NULL), hop, signal_len, window,
+ * w_host and the POWER / WELCH scaling as above.  Rows: STFT [S][nw][n/2 + 1] complex, unscaled, bins 0 ... n/2 of the frame's
+ * transform (DC and Nyquist bins have an imaginary part of exactly 0); POWER [S][nw][n/2 + 1] real; WELCH [S][n/2 + 1] real.
+ * The transform behind a frame is ONE complex transform of length n/2 on the reals read as pairs; where n/2 fits one hooked pass
+ * (n <= 8192 fp32, 4096 fp64) one launch reads the reals in place, windows them, transforms, splits the half-length spectrum
+ * into the n/2 + 1 bins and stores the rows: no widened copy, half the loaded bytes.  16-byte loads are used where every frame starts
+ * 16-byte aligned -- d_x 16-byte aligned, hop and signal_pitch multiples of 16 / sizeof(real) (4 fp32, 2 fp64) -- and reads
+ * component by component otherwise (any hop, pitch and base a real allows).  Every other n, and FFT_GPU_OPT_NO_FUSION: a pack
+ * kernel, the plain half-length transform, a split kernel, a power kernel.  fft_gpu_plan_info_hip: n = the frame length, batch =
+ * n_signals * nw, passes / factors of the length-n/2 core, fused = 1 on the one-launch path.  Executed by
+ * fft_gpu_execute_frames_hip with d_x real and signal_pitch in reals; fft_gpu_frames_count_hip, set_stream, sync, set_option and
+ * destroy as for complex frames plans. */
+fft_gpu_plan_t fft_gpu_plan_frames_real_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window,
+                                            const void* w_host /* n reals of prec, USER only */, fft_gpu_frames_out_t out, fft_precision_t prec);
 int fft_gpu_frames_count_hip(fft_gpu_plan_t plan);   /* nw = (signal_len - (n - hop)) / hop; -1: not a frames plan */
 /* async on the plan's stream.  d_x: complex signals, signal s at d_x + s * signal_pitch elements (0: signal_len; < signal_len: -1);
+ * a plan of fft_gpu_plan_frames_real_hip reads d_x as reals and counts signal_pitch in reals;
  * d_out: see fft_gpu_frames_out_t; it must not overlap d_x (d_out == d_x returns -1); sample_rate scales POWER and WELCH only */
 int fft_gpu_execute_frames_hip(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch /* 0: signal_len */,
                                void* d_out, double sample_rate);
@@ -277,6 +293,8 @@ int fft_gpu_bit_reverse(fft_gpu_memory_t in, fft_gpu_memory_t out, int n, int ba
 /* frames plans (fft_gpu_plan_frames_hip above) through the dispatcher */
 fft_gpu_plan_t fft_gpu_plan_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
                                    fft_gpu_frames_out_t out, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_frames_real(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                        fft_gpu_frames_out_t out, fft_precision_t prec);
 int fft_gpu_frames_count(fft_gpu_plan_t plan);
 int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch, void* d_out, double sample_rate);
 
