@@ -101,6 +101,10 @@ struct ExecHooks {
     // length, pre_tab the window packed in pairs (HOOK_MUL_PAIR), post_tab = W_2n^k (k < n, shared), and the rows that leave are the
     // n + 1 one-sided bins of the real transform: complex at out_pitch = n + 1, or power rows of n + 1 reals (TileHooks, HOOK bit 6)
     bool real_frames = false;
+    // single-pass plans only (execute_iframes): `in` holds one-sided rows of n + 1 bins of real transforms of length 2 n, row f at
+    // in + f * (n + 1); pre_tab = W_2n^k (k <= n, shared) is the c2r merge's table, and the rows that leave are the frames' 2 n real
+    // samples read as n complex values (TileHooks, HOOK bit 7)
+    bool herm_rows = false;
 };
 
 enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6, ALGO_MIXED_RADIX = 7 };
@@ -1285,6 +1289,16 @@ class Pow2Plan {
             if (hook_kind(p) == 1) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 8>, tp, -1, p);
             return;
         }
+        if (h.herm_rows) {  // one-sided rows in (execute_iframes): the hooked single-pass rows kernel with its Hermitian rows load
+            if (hook_kind(p) != 1 || side != 3) return;
+            k.pre_tab = h.pre_tab; k.pre_mode = HOOK_NONE;  // the merge's table, not a factor
+            k.n_in = (int)n;
+            tp.in_c = n + 1;
+            // rows of n + 1 bins: 16-byte aligned only where a bin is 16 bytes (fp64) and the base is
+            k.in_vec_ok = (V == 1 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+            launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 1 | 128>, tp, -1, p);
+            return;
+        }
         if (h.frames_per_signal > 0) {  // overlapping frames (execute_frames): the hooked single-pass rows kernel with its framed load
             if (hook_kind(p) != 1 || side != 3) return;
             const long long hop = h.in_pitch ? h.in_pitch : (h.real_frames ? 2 * n : n);
@@ -1316,7 +1330,7 @@ class Pow2Plan {
         }
         switch (hook_kind(p)) {
             // HOOK bits: 1 load side, 2 store side, 4 table values prefetched with the data, 8 round trip, 16 framed load, 32 one-sided
-            // power store, 64 real frames (fft_kernels.h)
+            // power store, 64 real frames, 128 Hermitian rows load (fft_kernels.h)
             case 1: launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3>, tp, -1, p); break;
             case 2: launch_kernel(tile_fft_kernel<T, 8, 1, FAM_R4, LOAD_CCONTIG, STORE_CCONTIG, true, 0, 1 | 4>, tp, -1, p); break;
             case 3: launch_hooked_fixed<FAM_SR16, LOAD_LCONTIG, STORE_CCONTIG, false, 2>(tp, p); break;
@@ -1352,6 +1366,16 @@ class Pow2Plan {
     void execute_frames(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
         run_if = nullptr;
         launch_pass_hooked(0, in, out, nf, false, (T)1, h, 3, 0);
+        rt->mark(0);
+    }
+
+    // ---- single-pass sizes: the nf rows of one launch are one-sided spectra of n + 1 bins (h.herm_rows, h.pre_tab = W_2n^k); the
+    // c2r merge rides on the load, the inverse transform is scaled by 1 / n, and out takes nf rows of n complex values -- the 2 n
+    // real samples of every frame, 1 / (2 n)-scaled like every inverse of the library.  Requires round_capable().
+    void execute_iframes(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
+        const long long n = 1ll << log2n;
+        run_if = nullptr;
+        launch_pass_hooked(0, in, out, nf, true, (T)(1.0L / (long double)n), h, 3, 0);
         rt->mark(0);
     }
 

@@ -307,7 +307,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -317,9 +317,11 @@ struct fft_gpu_plan {
     ffteng::FusedPlan<double, HipRT>* f64 = nullptr;
     ffteng::FramesPlan<float, HipRT>* w32 = nullptr;  // STFT / spectrogram / Welch on overlapping frames
     ffteng::FramesPlan<double, HipRT>* w64 = nullptr;
+    ffteng::IFramesPlan<float, HipRT>* i32 = nullptr;  // inverse STFT: one-sided rows -> real signals by overlap-add
+    ffteng::IFramesPlan<double, HipRT>* i64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6 };
 
 namespace {
 
@@ -423,6 +425,8 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
     if (p->f64) f(&p->f64->core);
     if (p->w32) f(&p->w32->core);
     if (p->w64) f(&p->w64->core);
+    if (p->i32) f(&p->i32->core);
+    if (p->i64) f(&p->i64->core);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -476,6 +480,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->r64) p->r64->execute_c2r((const fftk::cpx<double>*)d_in, (double*)d_out, p->batch);
     else if (p->f32 || p->f64) return -1;  // fused consumers take two inputs: fft_gpu_execute_fused_hip
     else if (p->w32 || p->w64) return -1;  // frames plans take a signal pitch and a sample rate: fft_gpu_execute_frames_hip
+    else if (p->i32 || p->i64) return -1;  // inverse frames plans take a signal pitch: fft_gpu_execute_iframes_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -738,6 +743,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->f64;
         delete p->w32;
         delete p->w64;
+        delete p->i32;
+        delete p->i64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -932,6 +939,55 @@ int fft_gpu_execute_frames_hip(fft_gpu_plan_t p, const void* d_x, long long sign
     DeviceGuard guard(p->device);
     const int rc = p->w32 ? p->w32->execute((const fftk::cpx<float>*)d_x, signal_pitch, d_out, sample_rate)
                           : p->w64->execute((const fftk::cpx<double>*)d_x, signal_pitch, d_out, sample_rate);
+    if (rc != 0) return -1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+// Inverse STFT by weighted overlap-add (fft_plans_ext.h IFramesPlan); w_host: the n window values of FFT_GPU_WINDOW_USER (host
+// memory, reals of `prec`), ignored otherwise
+fft_gpu_plan_t fft_gpu_plan_iframes_real_hip(int n, int hop, int n_frames, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                             fft_precision_t prec) {
+    if (n < 4 || (n & (n - 1)) != 0 || hop < 1 || hop > n || n_frames < 1 || n_signals < 1 || (int)window < 0 || (int)window > 4 ||
+        (window == FFT_GPU_WINDOW_USER && !w_host) || (long long)n_signals * n_frames > 0x7fffffff) {
+        fprintf(stderr, "fft_hip: invalid inverse frames plan arguments (n=%d hop=%d frames=%d signals=%d window=%d)\n", n, hop, n_frames, n_signals,
+                (int)window);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(n, n_signals * n_frames, 1, prec, PLAN_IFRAMES);
+    if (!p) return NULL;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->i32 = new (std::nothrow) ffteng::IFramesPlan<float, HipRT>();
+        ok = p->i32 && p->i32->build(&p->rt, n, hop, n_frames, n_signals, (int)window, (const float*)w_host);
+    } else {
+        p->i64 = new (std::nothrow) ffteng::IFramesPlan<double, HipRT>();
+        ok = p->i64 && p->i64->build(&p->rt, n, hop, n_frames, n_signals, (int)window, (const double*)w_host);
+    }
+    return finish_plan(p, ok, "inverse frames");
+}
+int fft_gpu_iframes_len_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->i32) return (int)p->i32->out_len();
+    if (p->i64) return (int)p->i64->out_len();
+    return -1;
+}
+int fft_gpu_iframes_unrecoverable_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->i32) return p->i32->unrecoverable;
+    if (p->i64) return p->i64->unrecoverable;
+    return -1;
+}
+// async on the plan's stream.  d_X: [signals][frames][n/2 + 1] complex; d_y: the real signals, signal_pitch reals apart (0: out_len)
+int fft_gpu_execute_iframes_hip(fft_gpu_plan_t p, const void* d_X, void* d_y, long long signal_pitch) {
+    if (!p || !d_X || !d_y || d_X == d_y || (!p->i32 && !p->i64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->i32 ? p->i32->execute((const fftk::cpx<float>*)d_X, (float*)d_y, signal_pitch)
+                          : p->i64->execute((const fftk::cpx<double>*)d_X, (double*)d_y, signal_pitch);
     if (rc != 0) return -1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1181,7 +1237,9 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->f64) p->f64->no_fusion = value != 0;
             if (p->w32) p->w32->no_fusion = value != 0;
             if (p->w64) p->w64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64) ? 0 : -1;
+            if (p->i32) p->i32->no_fusion = value != 0;
+            if (p->i64) p->i64->no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
@@ -1331,6 +1389,13 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->w32) fill_frames(p->w32);
     if (p->w64) fill_frames(p->w64);
+    auto fill_iframes = [&](auto* w) {  // n, batch = signals * frames, the half-length core's passes; fused: the merge rides on the pass's load
+        fill(&w->core);
+        info->fused = w->fused() ? 1 : 0;
+        info->workspace_bytes += (size_t)w->frames() * (size_t)(w->n / 2) * sizeof(*w->work);
+    };
+    if (p->i32) fill_iframes(p->i32);
+    if (p->i64) fill_iframes(p->i64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

@@ -107,6 +107,14 @@ struct TileHooks {
     //   X[0] = Re Z[0] + Im Z[0],  X[L] = Re Z[0] - Im Z[0]   (imaginary parts exactly 0)
     // Rows of L + 1 bins: complex at out + f * out_c, or with bit 5 one-sided power rows at power_out + f * (L + 1)
     // (|X[k]|^2 * power_scale, doubled for 0 < k < L).  Rows start only sizeof(cpx<T>)- / sizeof(T)-aligned: per-value stores.
+    // HOOK bit 7 (single-pass kernel only, with bit 0; never with bits 2 to 6): HERMITIAN ROWS load, the mirror image of bit 6's
+    // store.  Tile column t is frame f = c0 + t and reads the one-sided row in + f * in_c of L + 1 bins (in_c = L + 1, n_in = L)
+    // of a length-2L real transform; the column the stages start from is the c2r merge of that row,
+    //   E = (X[k] + conj X[L-k]) / 2,  O = (X[k] - conj X[L-k]) / 2 * conj(W_n^k),  Z[k] = E + i O,  W_n^k = pre_tab[k], k < L
+    // with X[0] and X[L] taken as REAL (their imaginary parts are never used: Re X[L] travels in the imaginary slot of X[0]).  The
+    // mirrored bin X[L-k] is read from the frame's own LDS row once the tile has landed.  pre_mode is HOOK_NONE: pre_tab is the
+    // merge's table, not a factor.  With inverse = 1 and scale = 1 / L the column that leaves is the frame's 2L real samples.
+    // Rows of L + 1 bins start only sizeof(cpx<T>)-aligned: in_vec_ok is 0 in fp32 (value-by-value loads).
 };
 
 template <typename T>
@@ -494,8 +502,9 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 // are prefetched together with the data (+ E * 4 VGPRs per group: the 2-waves-per-SIMD kernels; without it they are read
 // when the data is consumed -- the 4-waves-per-SIMD rows kernel, whose 128-VGPR budget has no room for them), bit 3 FFT ->
 // product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store, bit 6 real frames: packed real load and
-// the r2c split in the store (TileHooks; the last four on the hooked single-pass rows kernel only, bit 6 only with bits 0, 1
-// and 4).  Compile-time bits: an instantiation without one compiles to the code it had before.
+// the r2c split in the store, bit 7 Hermitian rows load: one-sided rows in, the c2r merge on the way to the stages (TileHooks;
+// the last five on the hooked single-pass rows kernel only, bit 6 only with bits 0, 1 and 4, bit 7 with bit 0 and none of bits
+// 2 to 6).  Compile-time bits: an instantiation without one compiles to the code it had before.
 // waves per SIMD the register budget of an instantiation is sized for.  The fp32 kernels with their shape baked in need only
 // 92-122 VGPRs when built for four waves per SIMD (no spills; built for two they take 150-250 because they may), i.e. two
 // 512-thread workgroups per CU.  Measured (profiles/r2_ab_rows_fixed.txt): the single-pass rows kernel gains 5...12 % from
@@ -572,6 +581,10 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
     static_assert(!(HK_FRAMES || HK_POWER || HK_REAL) || (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && HK_LOAD && HK_STORE),
                   "frames / power hooks: the hooked single-pass rows kernel only");
     static_assert(!HK_REAL || (HK_FRAMES && !HK_TABPF && !HK_ROUND && H == 1), "real frames: with the framed load on the hooked single-pass rows kernel only");
+    constexpr bool HK_HERM = (HOOK & 128) != 0;  // TileHooks: Hermitian rows load (one-sided rows in, the c2r merge before the stages)
+    static_assert(!HK_HERM || (E == 4 && FAM == FAM_R4 && LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && H == 1 && !TWIDDLE && HK_LOAD &&
+                               !(HOOK & (4 | 8 | 16 | 32 | 64))),
+                  "Hermitian rows load: on the hooked single-pass rows kernel only, with the load side and none of bits 2 to 6");
     vec16<T> nxttab[HK_TABPF ? DEPTH : 1][HK_TABPF ? H : 1][HK_TABPF ? E : 1];  // the load-side table values of the same chunks
     const bool pre_on = HK_LOAD && p.hk.pre_mode != HOOK_NONE;  // wave-uniform
     // index (inside its transform) of the first sample of lane-load i of group h, and its tile column / row
@@ -642,6 +655,9 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                             for (int vv = 0; vv < V; vv++)
                                 if (idx0 + vv < n_in) nxt[h][i].c[vv] = src[vv];
                         }
+                        // Hermitian rows: the chunk that holds X[0] also fetches Re X[L] into X[0]'s imaginary slot -- neither bin's own
+                        // imaginary part is ever used, and the row's LDS image then holds all the merge needs
+                        if (HK_HERM && idx0 == 0) nxt[h][i].c[0].im = reinterpret_cast<const T*>(src + L)[0];
                         if (HK_TABPF && pre_on) ntab[HK_TABPF ? h : 0][HK_TABPF ? i : 0] = *reinterpret_cast<const vec16<T>*>(p.hk.pre_tab + idx0);  // table padded to a multiple of V
                     }
                 } else if (live) {
@@ -758,6 +774,25 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     for (int vv = 0; vv < V; vv++)
                         x[h][e][vv] = *reinterpret_cast<const cpx<T>*>(smem + h * group_bytes + (size_t)(V * j + vv) * pitch +
                                                                        (size_t)l * SZ);
+                    if (HK_HERM) {
+                        // c2r merge of the frame's one-sided row (TileHooks, bit 7): slot e takes Z[l] from X[l] and X[L - l], both in the
+                        // frame's own LDS row, complete since the barrier above: no new barrier.  Element 0 of the row is (Re X[0], Re X[L]).
+                        // Padding columns hold zeros and merge to zeros.
+                        FFT_UNROLL
+                        for (int vv = 0; vv < V; vv++) {
+                            const cpx<T> a = x[h][e][vv];
+                            if (l == 0) {
+                                x[h][e][vv] = mk<T>((a.re + a.im) * (T)0.5, (a.re - a.im) * (T)0.5);
+                            } else {
+                                const cpx<T> m = *reinterpret_cast<const cpx<T>*>(smem + h * group_bytes + (size_t)(V * j + vv) * pitch +
+                                                                                  (size_t)(L - l) * SZ);
+                                const cpx<T> c = mk<T>(m.re, -m.im);  // conj X[L-l]
+                                const cpx<T> ev = cscale(cadd(a, c), (T)0.5);
+                                const cpx<T> od = cmul_conj(cscale(csub(a, c), (T)0.5), p.hk.pre_tab[l]);
+                                x[h][e][vv] = cadd(ev, mul_pos_i(od));
+                            }
+                        }
+                    }
                 }
             }
         }

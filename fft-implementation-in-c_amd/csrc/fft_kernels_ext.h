@@ -195,6 +195,64 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_mean_kernel(const T* power, T* psd
     }
 }
 
+// One-sided rows -> the complex rows a half-length inverse transform reads (the unfused path of the inverse frames plan): row f of
+// h + 1 bins at x_in + f * (h + 1) -> z[f][k], k < h, by the c2r merge
+//   E = (X[k] + conj X[h-k]) / 2,  O = (X[k] - conj X[h-k]) / 2 * conj(W_n^k),  Z[k] = E + i O
+// with X[0] and X[h] taken as REAL: their imaginary parts are never read into the result (numpy's irfft does the same;
+// c2r_merge_kernel lets them through).  One thread per value of z; `total` = frames * h.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) iframes_merge_kernel(const cpx<T>* x_in, cpx<T>* z, const cpx<T>* w, int h, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long f = i / h;
+        const int k = (int)(i - f * h);
+        const cpx<T>* xb = x_in + f * (h + 1);
+        if (k == 0) {
+            const T dc = xb[0].re, ny = xb[h].re;
+            z[i] = mk<T>((dc + ny) * (T)0.5, (dc - ny) * (T)0.5);
+        } else {
+            const cpx<T> a = xb[k];
+            const cpx<T> m = xb[h - k];
+            const cpx<T> c = mk<T>(m.re, -m.im);
+            const cpx<T> e = cscale(cadd(a, c), (T)0.5);
+            const cpx<T> o = cmul_conj(cscale(csub(a, c), (T)0.5), w[k]);
+            z[i] = cadd(e, mul_pos_i(o));
+        }
+    }
+}
+
+// Weighted overlap-add of windowed frames, normalised by the window envelope (the inverse frames plan's second step):
+//   y[s][t] = inv_env[t] * sum_w g[t - w hop] * v[s][w][t - w hop],   w over the frames that cover t,
+// v: [signals][nw][n] real frames, g: the n window values, inv_env: out_len = (nw - 1) hop + n values (0 where the envelope
+// vanishes: the sample is written as exactly 0, whatever the frames hold), y: signal s at y + s * signal_pitch.  One thread per
+// output sample, lanes along t (the reads of each frame and the stores are coalesced); w ascends inside the thread and the sum is
+// kept in double for both precisions.  No atomics: the result is bit-reproducible and independent of the grid.  Writes every
+// t < out_len of every signal and nothing else.  `total` = signals * out_len.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_overlap_add_kernel(const T* v, const T* g, const T* inv_env, T* y, long long signal_pitch, int n, int hop,
+                                                                  int nw, long long out_len, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long s = i / out_len;
+        const long long t = i - s * out_len;
+        const T ie = inv_env[t];
+        T r = (T)0;
+        if (ie != (T)0) {
+            long long w0 = t < n ? 0 : (t - n + hop) / hop;  // ceil((t - n + 1) / hop)
+            long long w1 = t / hop;
+            if (w1 > nw - 1) w1 = nw - 1;
+            const T* frames = v + s * (long long)nw * n;
+            double acc = 0.0;
+            for (long long w = w0; w <= w1; w++) {
+                const long long j = t - w * hop;
+                acc += (double)g[j] * (double)frames[w * n + j];
+            }
+            r = (T)(acc * (double)ie);
+        }
+        y[s * signal_pitch + t] = r;
+    }
+}
+
 // Device streams, 16 bytes per lane, `unroll` independent accesses in flight per thread, grid-stride: the practical ceiling
 // of the box the benchmark runs on (MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy).  MODE 0 copy, 1 read only (the
 // values are folded into one word that is stored only if it is a NaN pattern the inputs never hold), 2 write only.  NT: the

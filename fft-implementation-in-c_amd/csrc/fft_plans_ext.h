@@ -1,8 +1,8 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
-// overlapping frames).  Templated on the same runtime policy RT as the engine, so the unmodified source also runs in the CPU
-// emulation (tests/emu).
+// overlapping frames, and the inverse STFT by overlap-add).  Templated on the same runtime policy RT as the engine, so the
+// unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
 #include "fft_engine.h"
@@ -568,6 +568,123 @@ class FramesPlan {
         }
         if (out_kind == FRAMES_WELCH)
             launch_flat(rt, fftk::frames_mean_kernel<T>, (long long)n_signals * hb, (const T*)power, (T*)out, nw, hb, (long long)n_signals * hb);
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Inverse STFT: the way back from the real frames plan's STFT rows to real signals, by weighted overlap-add.
+//   X: [n_signals][nw][n/2 + 1] one-sided rows, contiguous (what FramesPlan with real_input writes as FRAMES_STFT);
+//   v_w = irfft_n(X[s][w]), scaled by 1/n (irfft(rfft(x)) = x); the imaginary parts of bins 0 and n/2 are ignored;
+//   env[t]  = sum_w g[t - w hop]^2,    y[s][t] = (sum_w g[t - w hop] v_w[t - w hop]) / env[t],    t < out_len = (nw - 1) hop + n,
+//   w over the frames that cover t, g the window (FramesPlan's own kinds: one window serves analysis and synthesis).  This is the
+//   least-squares inverse: y = x for X = stft(x) wherever env[t] > 0.  Where env[t] <= 1e-10 max g^2 (scipy's istft constant) the
+//   sample cannot be recovered: inv_env[t] = 0 and y[s][t] is written as exactly 0 (`unrecoverable` counts them per signal).
+//   Signal s starts at y + s * signal_pitch reals.
+// The core is the inverse transform of HALF the length, L = n/2, on the c2r merge of every row (RealPlan's identity).  Where L fits
+// one hook-capable pass the merge rides in that pass's load (tile_fft_kernel HOOK bit 7): one launch turns the rows into the
+// [frames][n] real workspace.  Every other n (n = 4 included), and no_fusion: iframes_merge_kernel and the plain core in place on
+// the workspace -- correct, not tuned.  frames_overlap_add_kernel then writes the signals.
+// ---------------------------------------------------------------------------
+template <typename T, typename RT>
+class IFramesPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    RT* rt = nullptr;
+    int n = 0, hop = 0, nw = 0, n_signals = 0, window = 0;
+    int unrecoverable = 0;    // samples per signal with a vanishing envelope (written as 0)
+    Pow2Plan<T, RT> core;     // length n/2
+    T* win = nullptr;         // the window, n reals
+    T* inv_env = nullptr;     // 1 / env[t], out_len reals (0 where env vanishes)
+    cpx<T>* wmerge = nullptr; // W_n^k, k <= n/2
+    cpx<T>* work = nullptr;   // [frames][n/2] complex = [frames][n] reals
+    bool ok = false;
+    bool no_fusion = false;
+    ~IFramesPlan() {
+        if (!rt) return;
+        rt->dfree(win); rt->dfree(inv_env); rt->dfree(wmerge); rt->dfree(work);
+    }
+    long long frames() const { return (long long)n_signals * nw; }
+    long long out_len() const { return (long long)(nw - 1) * hop + n; }
+    bool fused() const { return ok && !no_fusion && core.round_capable(); }
+
+    // w_host: n window values of type T (WINDOW_USER), ignored otherwise
+    bool build(RT* runtime, int n_, int hop_, int n_frames_, int n_signals_, int window_, const T* w_host) {
+        rt = runtime; n = n_; hop = hop_; nw = n_frames_; n_signals = n_signals_; window = window_;
+        if (n < 4 || (n & (n - 1)) != 0 || n > (1 << 29) || hop < 1 || hop > n || nw < 1 || n_signals < 1) return false;
+        if (window < WINDOW_RECT || window > WINDOW_USER || (window == WINDOW_USER && !w_host)) return false;
+        if (frames() > 0x7fffffff || frames() * (long long)n > (1ll << 40) || out_len() > 0x7fffffff) return false;
+        const int h = n / 2;
+        core.wants_hooks = true;
+        if (!core.build(rt, ilog2(h), ALGO_AUTO, (int)frames())) return false;
+        // the frames plans' windows (the reference's formulas with their n - 1 denominators, power_spectrum.c:5-25) as reals of T;
+        // the envelope is built from those ROUNDED values -- the ones the kernels multiply by -- in long double
+        std::vector<T> g((size_t)n);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        long double gmax2 = 0.0L;
+        for (int i = 0; i < n; i++) {
+            const long double a = two_pi * (long double)i / (long double)(n - 1);
+            long double w = 1.0L;
+            if (window == WINDOW_HANN) w = 0.5L * (1.0L - cosl(a));
+            else if (window == WINDOW_HAMMING) w = 0.54L - 0.46L * cosl(a);
+            else if (window == WINDOW_BLACKMAN) w = 0.42L - 0.5L * cosl(a) + 0.08L * cosl(2.0L * a);
+            else if (window == WINDOW_USER) w = (long double)w_host[i];
+            g[(size_t)i] = (T)w;
+            const long double g2 = (long double)g[(size_t)i] * (long double)g[(size_t)i];
+            if (g2 > gmax2) gmax2 = g2;
+        }
+        const long long ol = out_len();
+        std::vector<T> ie((size_t)ol);
+        unrecoverable = 0;
+        for (long long t = 0; t < ol; t++) {
+            const long long w0 = t < n ? 0 : (t - n + hop) / hop;
+            long long w1 = t / hop;
+            if (w1 > nw - 1) w1 = nw - 1;
+            long double env = 0.0L;
+            for (long long w = w0; w <= w1; w++) {
+                const long double gv = (long double)g[(size_t)(t - w * hop)];
+                env += gv * gv;
+            }
+            if (env > 1e-10L * gmax2) {
+                ie[(size_t)t] = (T)(1.0L / env);
+            } else {
+                ie[(size_t)t] = (T)0;
+                unrecoverable++;
+            }
+        }
+        std::vector<cpx<T>> tw;
+        make_twiddle_table<T>(tw, n, (long long)h + 1, 1);
+        win = (T*)rt->dmalloc((size_t)n * sizeof(T));
+        inv_env = (T*)rt->dmalloc((size_t)ol * sizeof(T));
+        wmerge = (cpx<T>*)rt->dmalloc(tw.size() * SZ);
+        work = (cpx<T>*)rt->dmalloc((size_t)frames() * (size_t)h * SZ);
+        if (!win || !inv_env || !wmerge || !work) return false;
+        rt->h2d(win, g.data(), (size_t)n * sizeof(T));
+        rt->h2d(inv_env, ie.data(), (size_t)ol * sizeof(T));
+        rt->h2d(wmerge, tw.data(), tw.size() * SZ);
+        ok = true;
+        return true;
+    }
+
+    // X: the one-sided rows; y: the signals (signal_pitch reals apart; 0: out_len).  0 / -1 (bad arguments: nothing is launched)
+    int execute(const cpx<T>* X, T* y, long long signal_pitch) {
+        if (!ok || !X || !y || (const void*)X == (const void*)y) return -1;
+        if (signal_pitch == 0) signal_pitch = out_len();
+        if (signal_pitch < out_len()) return -1;
+        const long long nf = frames();
+        const int h = n / 2;
+        if (fused()) {
+            ExecHooks<T> f;
+            f.herm_rows = true;
+            f.pre_tab = wmerge;
+            core.execute_iframes(X, work, (int)nf, f);
+        } else {
+            launch_flat(rt, fftk::iframes_merge_kernel<T>, nf * h, X, work, (const cpx<T>*)wmerge, h, nf * h);
+            core.execute(work, work, (int)nf, true);
+        }
+        const long long total = (long long)n_signals * out_len();
+        launch_flat(rt, fftk::frames_overlap_add_kernel<T>, total, reinterpret_cast<const T*>(work), (const T*)win, (const T*)inv_env, y, signal_pitch, n, hop,
+                    nw, out_len(), total);
         return 0;
     }
 };

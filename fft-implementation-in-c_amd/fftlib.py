@@ -69,6 +69,8 @@ SIGNATURES = {
     "fft_gpu_plan_frames_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count_hip": (_i, [_vp]),
     "fft_gpu_plan_frames_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_execute_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
+    "fft_gpu_plan_iframes_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i]), "fft_gpu_iframes_len_hip": (_i, [_vp]),
+    "fft_gpu_iframes_unrecoverable_hip": (_i, [_vp]), "fft_gpu_execute_iframes_hip": (_i, [_vp, _vp, _vp, C.c_longlong]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -92,6 +94,8 @@ SIGNATURES = {
     "fft_gpu_plan_frames": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_frames_count": (_i, [_vp]),
     "fft_gpu_plan_frames_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_execute_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
+    "fft_gpu_plan_iframes_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i]), "fft_gpu_iframes_len": (_i, [_vp]),
+    "fft_gpu_iframes_unrecoverable": (_i, [_vp]), "fft_gpu_execute_iframes": (_i, [_vp, _vp, _vp, C.c_longlong]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -340,6 +344,30 @@ class ExtPlan:
             return (self.n_signals, self.nw, self.n // 2 + 1), rdt
         return (self.n_signals, self.n // 2 + 1), rdt
 
+    @classmethod
+    def iframes(cls, n, hop, n_frames, n_signals=1, window="hann", dtype=np.float64):
+        """Inverse STFT plan (fft_gpu_plan_iframes_real_hip): [n_signals, n_frames, n//2 + 1] one-sided rows -> n_signals real signals
+        of out_len = (n_frames - 1) * hop + n samples of dtype float32 / float64, by weighted overlap-add.  window: a name of WINDOWS,
+        or n real values (USER).  unrecoverable: the samples per signal whose window envelope vanishes (written as 0)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("an inverse frames plan writes float32 or float64 signals")
+        w = None
+        if not isinstance(window, str):
+            w = np.ascontiguousarray(np.asarray(window).astype(dt))
+            if w.shape != (n,):
+                raise ValueError("a user window has n values")
+        p = cls(init().fft_gpu_plan_iframes_real_hip(n, hop, n_frames, n_signals, WINDOWS["user" if w is not None else window],
+                                                     None if w is None else w.ctypes.data, PREC_F32 if dt == np.float32 else PREC_F64))
+        p.n, p.hop, p.nw, p.n_signals, p.dtype = n, hop, n_frames, n_signals, dt
+        p.out_len = p.lib.fft_gpu_iframes_len_hip(p.handle)
+        p.unrecoverable = p.lib.fft_gpu_iframes_unrecoverable_hip(p.handle)
+        return p
+
+    def execute_iframes(self, d_X, d_y, signal_pitch=0):
+        if self.lib.fft_gpu_execute_iframes_hip(self.handle, d_X, d_y, signal_pitch) != 0:
+            raise RuntimeError("fft_gpu_execute_iframes_hip failed")
+
     def set_stream(self, stream_ptr):
         self.lib.fft_gpu_plan_set_stream(self.handle, stream_ptr)
 
@@ -476,6 +504,31 @@ def stft(x, n, hop, window="hann"):
     A float32 / float64 x (here, in spectrogram and in welch) is read as real signals where it lies -- no complex copy -- and
     the rows are one-sided: [signals, frames, n//2 + 1]."""
     return _frames(x, n, hop, window, "stft", 1.0)
+
+
+def istft(X, n, hop, window="hann"):
+    """X: [signals, frames, n//2 + 1] (or [frames, n//2 + 1]) complex64 / complex128, the one-sided rows stft() returns for real
+    signals -> [signals, out_len] float32 / float64, out_len = (frames - 1) * hop + n: the least-squares inverse by weighted
+    overlap-add with the same window, istft(stft(x)) = x wherever the window envelope does not vanish (those samples are 0)."""
+    X = np.ascontiguousarray(X)
+    if X.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+        raise ValueError("istft takes complex64 or complex128 rows")
+    X3 = X.reshape((1,) + X.shape) if X.ndim == 2 else X
+    if X3.ndim != 3 or X3.shape[2] != n // 2 + 1:
+        raise ValueError("istft takes [signals, frames, n//2 + 1] rows")
+    rdt = np.dtype(np.float32 if X.dtype == np.complex64 else np.float64)
+    plan = ExtPlan.iframes(n, hop, X3.shape[1], X3.shape[0], window, rdt)
+    shape = (X3.shape[0], plan.out_len)
+    a, o = DeviceBuffer(X3.nbytes), DeviceBuffer(shape[0] * shape[1] * rdt.itemsize)
+    a.upload(X3)
+    plan.execute_iframes(a.ptr, o.ptr, 0)
+    if plan.sync() != 0:
+        raise RuntimeError("execute failed")
+    res = o.download(shape, rdt)
+    a.free()
+    o.free()
+    plan.destroy()
+    return res[0] if X.ndim == 2 else res
 
 
 def spectrogram(x, n, hop, window="hann", fs=1.0):

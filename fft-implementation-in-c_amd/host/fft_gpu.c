@@ -206,6 +206,22 @@ int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signa
     return fft_gpu_execute_frames_hip(plan, d_x, signal_pitch, d_out, sample_rate);
 }
 
+/* inverse STFT plans: one-sided rows back to real signals by overlap-add */
+fft_gpu_plan_t fft_gpu_plan_iframes_real(int n, int hop, int n_frames, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                         fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_iframes_real")) return NULL;
+    return fft_gpu_plan_iframes_real_hip(n, hop, n_frames, n_signals, window, w_host, prec);
+}
+
+int fft_gpu_iframes_len(fft_gpu_plan_t plan) { return fft_gpu_iframes_len_hip(plan); }
+
+int fft_gpu_iframes_unrecoverable(fft_gpu_plan_t plan) { return fft_gpu_iframes_unrecoverable_hip(plan); }
+
+int fft_gpu_execute_iframes(fft_gpu_plan_t plan, const void* d_X, void* d_y, long long signal_pitch) {
+    if (!backend_is_hip("fft_gpu_execute_iframes")) return -1;
+    return fft_gpu_execute_iframes_hip(plan, d_X, d_y, signal_pitch);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

@@ -113,7 +113,7 @@ typedef enum {
     FFT_GPU_OPT_TEAM_ENABLE = 2,         /* 0: run the multi-pass schedule only; 1: back to the team kernel where the plan has one */
     FFT_GPU_OPT_NO_FUSION = 3,           /* 1: Bluestein / fused-consumer plans run their element-wise steps as kernels of their own
                                             instead of fusing them into the FFT passes (same results to rounding; tests); frames plans
-                                            run their per-signal fallback */
+                                            run their per-signal fallback, inverse frames plans their merge kernel + plain inverse */
     FFT_GPU_OPT_NO_CHAIN = 4,            /* 1: Bluestein / fused-consumer plans keep the forward transform's last pass and the inverse
                                             transform's first pass as two kernels (by default they run as one where their tiles agree
                                             and the transform has >= 2^19 points; tests); 2: as one wherever the tiles agree (tools) */
@@ -223,6 +223,32 @@ int fft_gpu_frames_count_hip(fft_gpu_plan_t plan);   /* nw = (signal_len - (n - 
  * d_out: see fft_gpu_frames_out_t; it must not overlap d_x (d_out == d_x returns -1); sample_rate scales POWER and WELCH only */
 int fft_gpu_execute_frames_hip(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch /* 0: signal_len */,
                                void* d_out, double sample_rate);
+/* Inverse STFT of real signals by weighted overlap-add: the way back from fft_gpu_plan_frames_real_hip's STFT rows.  d_X holds
+ * n_signals * n_frames one-sided rows of n/2 + 1 complex bins of `prec`, contiguous ([S][nw][n/2 + 1], exactly what the real
+ * frames plan's STFT writes); the result is n_signals REAL signals of out_len = (n_frames - 1) * hop + n samples.  With
+ * v_w = irfft_n(X[s][w]) -- scaled by 1/n, so that irfft(rfft(x)) = x like every inverse of the library; the imaginary parts of
+ * bins 0 and n/2 are ignored, as numpy's irfft does -- and g the window (same kinds and formulas as the frames plans: one window
+ * serves analysis and synthesis):
+ *     env[t] = sum_w g[t - w hop]^2,    y[s][t] = (sum_w g[t - w hop] v_w[t - w hop]) / env[t]      (w: the frames that cover t)
+ * the least-squares inverse: it returns x exactly for X = stft(x) wherever env[t] > 0.  1 / env is a plan-time table (long double).
+ * Where env[t] <= 1e-10 max g^2 (scipy's istft constant; e.g. the two end samples under the symmetric Hann window) the sample cannot
+ * be recovered and y[s][t] is written as exactly 0; fft_gpu_iframes_unrecoverable_hip counts those samples of one signal.
+ * n: a power of two >= 4; 1 <= hop <= n; n_frames, n_signals >= 1; n_frames * n_signals <= 2^31 - 1 and frames * n <= 2^40; a USER
+ * window needs w_host; anything else, or a failed allocation, returns NULL.  The transform behind a frame is ONE inverse complex
+ * transform of length n/2; where that fits one hooked pass (n <= 8192 fp32, 4096 fp64; not n = 4) one launch reads the one-sided
+ * rows, merges them on the way in and writes the [frames][n] real workspace (allocated at plan time).  Every other n, and
+ * FFT_GPU_OPT_NO_FUSION: a merge kernel and the plain half-length inverse.  The overlap-add kernel (double accumulation, no atomics:
+ * bit-reproducible) then writes every sample t < out_len of every signal and nothing else.  fft_gpu_plan_info_hip: n = the frame
+ * length, batch = n_signals * n_frames, direction +1, passes / factors of the length-n/2 core, fused = 1 on the one-launch transform
+ * path.  set_stream, sync, set_option and destroy as for frames plans. */
+fft_gpu_plan_t fft_gpu_plan_iframes_real_hip(int n, int hop, int n_frames, int n_signals, fft_gpu_window_t window,
+                                             const void* w_host /* n reals of prec, USER only */, fft_precision_t prec);
+int fft_gpu_iframes_len_hip(fft_gpu_plan_t plan);            /* out_len; -1: not such a plan */
+int fft_gpu_iframes_unrecoverable_hip(fft_gpu_plan_t plan);  /* samples per signal written as 0; -1: not such a plan */
+/* async on the plan's stream.  d_X: the one-sided rows; d_y: the real signals, signal s at d_y + s * signal_pitch reals (0: out_len;
+ * < out_len: -1); the signal_pitch - out_len reals between signals are never touched.  NULL pointers and d_X == d_y return -1;
+ * nothing is launched then. */
+int fft_gpu_execute_iframes_hip(fft_gpu_plan_t plan, const void* d_X, void* d_y, long long signal_pitch /* 0: out_len */);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
@@ -297,6 +323,12 @@ fft_gpu_plan_t fft_gpu_plan_frames_real(int n, int hop, int signal_len, int n_si
                                         fft_gpu_frames_out_t out, fft_precision_t prec);
 int fft_gpu_frames_count(fft_gpu_plan_t plan);
 int fft_gpu_execute_frames(fft_gpu_plan_t plan, const void* d_x, long long signal_pitch, void* d_out, double sample_rate);
+/* inverse frames plans (fft_gpu_plan_iframes_real_hip above) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_iframes_real(int n, int hop, int n_frames, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                         fft_precision_t prec);
+int fft_gpu_iframes_len(fft_gpu_plan_t plan);
+int fft_gpu_iframes_unrecoverable(fft_gpu_plan_t plan);
+int fft_gpu_execute_iframes(fft_gpu_plan_t plan, const void* d_X, void* d_y, long long signal_pitch);
 
 #ifdef __cplusplus
 }
