@@ -307,7 +307,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -319,9 +319,11 @@ struct fft_gpu_plan {
     ffteng::FramesPlan<double, HipRT>* w64 = nullptr;
     ffteng::IFramesPlan<float, HipRT>* i32 = nullptr;  // inverse STFT: one-sided rows -> real signals by overlap-add
     ffteng::IFramesPlan<double, HipRT>* i64 = nullptr;
+    ffteng::CrossFramesPlan<float, HipRT>* x32 = nullptr;  // cross-spectral density / coherence / transfer estimate on the frames of signal pairs
+    ffteng::CrossFramesPlan<double, HipRT>* x64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7 };
 
 namespace {
 
@@ -427,6 +429,8 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
     if (p->w64) f(&p->w64->core);
     if (p->i32) f(&p->i32->core);
     if (p->i64) f(&p->i64->core);
+    if (p->x32) f(&p->x32->inner.core);
+    if (p->x64) f(&p->x64->inner.core);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -481,6 +485,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->f32 || p->f64) return -1;  // fused consumers take two inputs: fft_gpu_execute_fused_hip
     else if (p->w32 || p->w64) return -1;  // frames plans take a signal pitch and a sample rate: fft_gpu_execute_frames_hip
     else if (p->i32 || p->i64) return -1;  // inverse frames plans take a signal pitch: fft_gpu_execute_iframes_hip
+    else if (p->x32 || p->x64) return -1;  // cross frames plans take two signals: fft_gpu_execute_cross_frames_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -745,6 +750,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->w64;
         delete p->i32;
         delete p->i64;
+        delete p->x32;
+        delete p->x64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -930,6 +937,8 @@ int fft_gpu_frames_count_hip(fft_gpu_plan_t p) {
     if (!p) return -1;
     if (p->w32) return p->w32->nw;
     if (p->w64) return p->w64->nw;
+    if (p->x32) return p->x32->inner.nw;
+    if (p->x64) return p->x64->inner.nw;
     return -1;
 }
 // async on the plan's stream.  d_x: the signals, signal_pitch elements apart (0: signal_len; reals for a real frames plan, which
@@ -988,6 +997,61 @@ int fft_gpu_execute_iframes_hip(fft_gpu_plan_t p, const void* d_X, void* d_y, lo
     DeviceGuard guard(p->device);
     const int rc = p->i32 ? p->i32->execute((const fftk::cpx<float>*)d_X, (float*)d_y, signal_pitch)
                           : p->i64->execute((const fftk::cpx<double>*)d_X, (double*)d_y, signal_pitch);
+    if (rc != 0) return -1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+// Cross-spectral density, coherence and H1 transfer estimate of signal pairs on overlapping frames (fft_plans_ext.h CrossFramesPlan);
+// arguments as for the frames plans, out: fft_gpu_cross_out_t
+static fft_gpu_plan_t plan_cross(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host, fft_gpu_cross_out_t out,
+                                 fft_precision_t prec, bool real_input) {
+    if (n < (real_input ? 4 : 2) || (n & (n - 1)) != 0 || hop < 1 || hop > n || signal_len < n || n_signals < 1 || (int)window < 0 || (int)window > 4 ||
+        (window == FFT_GPU_WINDOW_USER && !w_host) || (int)out < 0 || (int)out > 3 ||
+        (long long)n_signals * ((signal_len - (n - hop)) / hop) > 0x7fffffff) {
+        fprintf(stderr, "fft_hip: invalid cross frames plan arguments (n=%d hop=%d signal_len=%d signals=%d window=%d out=%d)\n", n, hop, signal_len,
+                n_signals, (int)window, (int)out);
+        return NULL;
+    }
+    const int nw = (signal_len - (n - hop)) / hop;
+    fft_gpu_plan* p = new_plan_shell(n, n_signals * nw, -1, prec, PLAN_CROSS);
+    if (!p) return NULL;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->x32 = new (std::nothrow) ffteng::CrossFramesPlan<float, HipRT>();
+        ok = p->x32 && p->x32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out, real_input);
+    } else {
+        p->x64 = new (std::nothrow) ffteng::CrossFramesPlan<double, HipRT>();
+        ok = p->x64 && p->x64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out, real_input);
+    }
+    return finish_plan(p, ok, real_input ? "real cross frames" : "cross frames");
+}
+fft_gpu_plan_t fft_gpu_plan_cross_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                             fft_gpu_cross_out_t out, fft_precision_t prec) {
+    return plan_cross(n, hop, signal_len, n_signals, window, w_host, out, prec, false);
+}
+fft_gpu_plan_t fft_gpu_plan_cross_frames_real_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                                  fft_gpu_cross_out_t out, fft_precision_t prec) {
+    return plan_cross(n, hop, signal_len, n_signals, window, w_host, out, prec, true);
+}
+// frames per chunk of the reduction (a function of nw, n_signals and n alone); -1: not a cross frames plan
+int fft_gpu_cross_chunk_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->x32) return p->x32->C;
+    if (p->x64) return p->x64->C;
+    return -1;
+}
+// async on the plan's stream.  d_x, d_y: the signals of every pair, each side with its own pitch in elements (reals for a real plan;
+// 0: signal_len); d_x == d_y is legal; d_out (see fft_gpu_cross_out_t) must overlap neither
+int fft_gpu_execute_cross_frames_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch, void* d_out,
+                                     double sample_rate) {
+    if (!p || !d_x || !d_y || !d_out || (!p->x32 && !p->x64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->x32 ? p->x32->execute(d_x, x_pitch, d_y, y_pitch, d_out, sample_rate) : p->x64->execute(d_x, x_pitch, d_y, y_pitch, d_out, sample_rate);
     if (rc != 0) return -1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1239,7 +1303,9 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->w64) p->w64->no_fusion = value != 0;
             if (p->i32) p->i32->no_fusion = value != 0;
             if (p->i64) p->i64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64) ? 0 : -1;
+            if (p->x32) p->x32->inner.no_fusion = value != 0;
+            if (p->x64) p->x64->inner.no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
@@ -1396,6 +1462,13 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->i32) fill_iframes(p->i32);
     if (p->i64) fill_iframes(p->i64);
+    auto fill_cross = [&](auto* c) {  // n, batch = signals * frames, the inner frames plan's core and path; chunk_batch: frames per chunk of the reduction
+        fill_frames(&c->inner);
+        info->chunk_batch = c->C;
+        info->workspace_bytes += 2 * c->rows_bytes() + c->part_bytes();
+    };
+    if (p->x32) fill_cross(p->x32);
+    if (p->x64) fill_cross(p->x64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

@@ -253,6 +253,94 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_overlap_add_kernel(const T* v, con
     }
 }
 
+// The cross kernels below rest on exact identities (Im conj(X) X == 0, swapped inputs give the conjugate bit for bit): a product
+// and the sum it enters must round separately, so the compiler may not contract them into an fma.
+#if defined(__clang__)
+#define FFT_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define FFT_NO_CONTRACT
+#endif
+
+enum { CROSS_CSD = 0, CROSS_COHERENCE = 1, CROSS_TRANSFER = 2, CROSS_ALL = 3 };
+
+// Two sets of STFT rows -> partial sums of the auto and cross spectra (the cross frames plan's first step).
+//   X, Y: rows of frame f = s * nw + w at X + f * pitch (bins 0 .. hb - 1 are read: pitch = hb for one-sided rows, n for full ones);
+//   part[s][c][k][0..3] = sum over the frames w of chunk c (w = c * C .. min(nw, (c + 1) * C) - 1, ascending) of
+//       |X_w[k]|^2,  |Y_w[k]|^2,  Re conj(X_w[k]) Y_w[k],  Im conj(X_w[k]) Y_w[k].
+// One thread per (pair, chunk, bin), lanes along k: both row reads are coalesced, as is the store.  Products and sums are formed in
+// double for both precisions (memory bound; the error must not grow with the frame count), never contracted.  No atomics: the
+// result is bit-reproducible and independent of the grid.  `total` = signals * chunks * hb.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_cross_partial_kernel(const cpx<T>* X, const cpx<T>* Y, long long pitch, double* part, int nw, int hb,
+                                                                    int C, int chunks, long long total) {
+    FFT_NO_CONTRACT
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long sc = i / hb;
+        const int k = (int)(i - sc * hb);
+        const long long s = sc / chunks;
+        const long long c = sc - s * chunks;
+        const long long w0 = c * (long long)C;
+        long long w1 = w0 + C;
+        if (w1 > nw) w1 = nw;
+        const cpx<T>* xr = X + (s * nw + w0) * pitch + k;
+        const cpx<T>* yr = Y + (s * nw + w0) * pitch + k;
+        double sxx = 0.0, syy = 0.0, sre = 0.0, sim = 0.0;
+        for (long long w = w0; w < w1; w++, xr += pitch, yr += pitch) {
+            const cpx<T> a = *xr, b = *yr;
+            const double ar = (double)a.re, ai = (double)a.im, br = (double)b.re, bi = (double)b.im;
+            sxx += ar * ar + ai * ai;
+            syy += br * br + bi * bi;
+            sre += ar * br + ai * bi;
+            sim += ar * bi - ai * br;
+        }
+        double* p = part + i * 4;
+        p[0] = sxx; p[1] = syy; p[2] = sre; p[3] = sim;
+    }
+}
+
+// Partial sums -> the output rows of the cross frames plan (its second step).  One thread per (pair, bin): the chunks are summed in
+// ascending order in double, scaled by c_k / nw (c_k = base, doubled for 0 < k < hb - 1: the POWER / WELCH scaling), the output
+// kind is formed in double and rounded ONCE to T:
+//   CROSS_CSD        out[s][k] = Pxy                                  complex
+//   CROSS_COHERENCE  out[s][k] = |Pxy|^2 / (Pxx Pyy), 0 where Pxx Pyy == 0    real
+//   CROSS_TRANSFER   out[s][k] = Pxy / Pxx, (0, 0) where Pxx == 0              complex
+//   CROSS_ALL        out[s][k][0..3] = Pxx, Pyy, Re Pxy, Im Pxy               reals
+// (a NaN is not "== 0": it propagates).  Writes its rows and nothing else.  `total` = signals * hb.
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) frames_cross_finish_kernel(const double* part, T* out, int nw, int hb, int chunks, double base, int kind,
+                                                                   long long total) {
+    FFT_NO_CONTRACT
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long s = i / hb;
+        const int k = (int)(i - s * hb);
+        const double* p = part + (s * chunks * hb + k) * 4;
+        double sxx = 0.0, syy = 0.0, sre = 0.0, sim = 0.0;
+        for (int c = 0; c < chunks; c++, p += (long long)hb * 4) {
+            sxx += p[0]; syy += p[1]; sre += p[2]; sim += p[3];
+        }
+        const double f = ((k > 0 && k < hb - 1) ? base * 2.0 : base) / (double)nw;
+        const double pxx = sxx * f, pyy = syy * f, pre = sre * f, pim = sim * f;
+        if (kind == CROSS_CSD) {
+            out[2 * i] = (T)pre;
+            out[2 * i + 1] = (T)pim;
+        } else if (kind == CROSS_COHERENCE) {
+            const double den = pxx * pyy;
+            out[i] = den == 0.0 ? (T)0 : (T)((pre * pre + pim * pim) / den);
+        } else if (kind == CROSS_TRANSFER) {
+            const bool z = pxx == 0.0;
+            out[2 * i] = z ? (T)0 : (T)(pre / pxx);
+            out[2 * i + 1] = z ? (T)0 : (T)(pim / pxx);
+        } else {
+            out[4 * i] = (T)pxx;
+            out[4 * i + 1] = (T)pyy;
+            out[4 * i + 2] = (T)pre;
+            out[4 * i + 3] = (T)pim;
+        }
+    }
+}
+
 // Device streams, 16 bytes per lane, `unroll` independent accesses in flight per thread, grid-stride: the practical ceiling
 // of the box the benchmark runs on (MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy).  MODE 0 copy, 1 read only (the
 // values are folded into one word that is stored only if it is a NaN pattern the inputs never hold), 2 write only.  NT: the

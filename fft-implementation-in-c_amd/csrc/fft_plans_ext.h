@@ -689,4 +689,103 @@ class IFramesPlan {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Two-signal statistics on the same frames: cross-spectral density, magnitude-squared coherence, H1 transfer estimate (scipy's
+// csd / coherence; what the reference's compute_coherence, applications/power_spectrum.c:195-224, leaves as a placeholder).
+//   pairs (x[s], y[s]), s < n_signals, of signal_len samples each, every side with its own base and pitch; frames, windows, nw and
+//   P are FramesPlan's; X_w, Y_w the STFT rows of frame w, hb = n/2 + 1 bins; c_k = 1 / (sample_rate * P), doubled for 0 < k < n/2:
+//       Pxx[k] = c_k mean_w |X_w[k]|^2,   Pyy[k] = c_k mean_w |Y_w[k]|^2,   Pxy[k] = c_k mean_w conj(X_w[k]) Y_w[k]
+//   out: see fftk::frames_cross_finish_kernel (CROSS_CSD / COHERENCE / TRANSFER / ALL).
+// The plan owns ONE FramesPlan in FRAMES_STFT mode, used unchanged (real or complex input, its fused path or its fallback), and runs
+// it on x and on y into two row workspaces ([frames][hb] one-sided rows for real input, [frames][n] for complex input, of which
+// bins 0 .. n/2 are read); frames_cross_partial_kernel then reduces chunks of C frames to double partial sums and
+// frames_cross_finish_kernel sums the chunks and forms the output.
+// The chunk length is a function of (nw, n_signals, hb) alone -- never of the grid or the device, so results do not depend on
+// either: C = max(kMinChunk, ceil(nw / ceil(kTargetThreads / (n_signals * hb)))), chunks = ceil(nw / C).  kTargetThreads = 2^18
+// threads (four waves per SIMD of a 256-CU device) for few long signals; C >= 32 frames keeps the partial sums (32 bytes per chunk
+// and bin) at or below 1/16 of the rows they sum up.  Both figures are guesses until timed.
+// ---------------------------------------------------------------------------
+template <typename T, typename RT>
+class CrossFramesPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr long long kTargetThreads = 1ll << 18;
+    static constexpr int kMinChunk = 32;
+    RT* rt = nullptr;
+    FramesPlan<T, RT> inner;
+    int out_kind = 0;
+    int C = 0, chunks = 0;
+    long long row_pitch = 0;    // elements between the rows of a workspace
+    cpx<T>* rows_x = nullptr;   // [frames][row_pitch]
+    cpx<T>* rows_y = nullptr;
+    double* part = nullptr;     // [n_signals][chunks][hb][4]
+    int max_grid = 16384, block = 256;  // launch geometry of the two kernels (the results do not depend on it: tests vary it)
+    bool ok = false;
+    ~CrossFramesPlan() {
+        if (!rt) return;
+        rt->dfree(rows_x); rt->dfree(rows_y); rt->dfree(part);
+    }
+    static int chunk_len(int nw, int n_signals, int hb) {
+        const long long per_chunk = (long long)n_signals * hb;
+        const long long want = (kTargetThreads + per_chunk - 1) / per_chunk;
+        const long long c = ((long long)nw + want - 1) / want;
+        return c < kMinChunk ? kMinChunk : (int)c;
+    }
+    int bins() const { return inner.bins(); }
+    size_t rows_bytes() const { return (size_t)inner.frames() * (size_t)row_pitch * SZ; }
+    size_t part_bytes() const { return (size_t)inner.n_signals * (size_t)chunks * (size_t)bins() * 4 * sizeof(double); }
+    // values of T per (pair, bin) of the output
+    int out_width() const { return out_kind == fftk::CROSS_COHERENCE ? 1 : out_kind == fftk::CROSS_ALL ? 4 : 2; }
+
+    bool build(RT* runtime, int n, int hop, int signal_len, int n_signals, int window, const T* w_host, int out_kind_, bool real_input) {
+        rt = runtime; out_kind = out_kind_;
+        if (out_kind < fftk::CROSS_CSD || out_kind > fftk::CROSS_ALL) return false;
+        if (!inner.build(rt, n, hop, signal_len, n_signals, window, w_host, FRAMES_STFT, real_input)) return false;
+        if (!(inner.window_power > 0.0L)) return false;
+        C = chunk_len(inner.nw, n_signals, bins());
+        chunks = (inner.nw + C - 1) / C;
+        row_pitch = real_input ? bins() : n;
+        rows_x = (cpx<T>*)rt->dmalloc(rows_bytes());
+        rows_y = (cpx<T>*)rt->dmalloc(rows_bytes());
+        part = (double*)rt->dmalloc(part_bytes());
+        if (!rows_x || !rows_y || !part) return false;
+        ok = true;
+        return true;
+    }
+
+    template <class K, class... A>
+    void launch(K kernel, long long total, A... args) {
+        long long g = (total + block - 1) / block;
+        if (g > max_grid) g = max_grid;
+        if (g < 1) g = 1;
+        rt->launch(kernel, g, block, (size_t)0, args...);
+    }
+
+    // x, y: the signals of every pair (pitches in elements -- reals for real input; 0: signal_len); x == y is legal; out must
+    // overlap neither.  0 / -1 (bad arguments: nothing is launched)
+    int execute(const void* x, long long x_pitch, const void* y, long long y_pitch, void* out, double sample_rate) {
+        if (!ok || !x || !y || !out) return -1;
+        if (x_pitch == 0) x_pitch = inner.signal_len;
+        if (y_pitch == 0) y_pitch = inner.signal_len;
+        if (x_pitch < inner.signal_len || y_pitch < inner.signal_len) return -1;
+        const long long S = inner.n_signals;
+        const int hb = bins();
+        const size_t esz = inner.real_input ? sizeof(T) : (size_t)SZ;
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)S * hb * out_width() * sizeof(T);
+        const uintptr_t in[2] = {(uintptr_t)x, (uintptr_t)y};
+        const long long pitch[2] = {x_pitch, y_pitch};
+        for (int i = 0; i < 2; i++) {
+            const uintptr_t i1 = in[i] + (size_t)((S - 1) * pitch[i] + inner.signal_len) * esz;
+            if (o0 < i1 && in[i] < o1) return -1;
+        }
+        if (inner.execute((const cpx<T>*)x, x_pitch, rows_x, 1.0) != 0) return -1;
+        if (inner.execute((const cpx<T>*)y, y_pitch, rows_y, 1.0) != 0) return -1;
+        const double base = (double)(1.0L / ((long double)sample_rate * inner.window_power));
+        const long long tp = S * chunks * hb;
+        launch(fftk::frames_cross_partial_kernel<T>, tp, (const cpx<T>*)rows_x, (const cpx<T>*)rows_y, row_pitch, part, inner.nw, hb, C, chunks, tp);
+        launch(fftk::frames_cross_finish_kernel<T>, S * hb, (const double*)part, (T*)out, inner.nw, hb, chunks, base, out_kind, S * hb);
+        return 0;
+    }
+};
+
 }  // namespace ffteng

@@ -71,6 +71,9 @@ SIGNATURES = {
     "fft_gpu_execute_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_plan_iframes_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i]), "fft_gpu_iframes_len_hip": (_i, [_vp]),
     "fft_gpu_iframes_unrecoverable_hip": (_i, [_vp]), "fft_gpu_execute_iframes_hip": (_i, [_vp, _vp, _vp, C.c_longlong]),
+    "fft_gpu_plan_cross_frames_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
+    "fft_gpu_plan_cross_frames_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_cross_chunk_hip": (_i, [_vp]),
+    "fft_gpu_execute_cross_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -96,6 +99,9 @@ SIGNATURES = {
     "fft_gpu_execute_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_plan_iframes_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i]), "fft_gpu_iframes_len": (_i, [_vp]),
     "fft_gpu_iframes_unrecoverable": (_i, [_vp]), "fft_gpu_execute_iframes": (_i, [_vp, _vp, _vp, C.c_longlong]),
+    "fft_gpu_plan_cross_frames": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
+    "fft_gpu_plan_cross_frames_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_cross_chunk": (_i, [_vp]),
+    "fft_gpu_execute_cross_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_double]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -110,12 +116,16 @@ SIGNATURES = {
     "compute_periodogram_gpu": (_vp, [_vp, _i, C.c_double]), "autocorrelation_fft_gpu": (_vp, [_vp, _i]),
     "cross_correlation_fft_gpu": (_vp, [_vp, _vp, _i]),
     "fft_welch_psd_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]), "fft_welch_psd_real_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]),
+    "fft_coherence_real_gpu": (_vp, [_vp, _vp, _i, _i, _i]), "fft_csd_real_gpu": (_i, [_vp, _vp, _i, C.c_double, _i, _i, _vp]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
     "radix4_fft_gpu": (_i, [_vp, _i, _i]), "split_radix_fft_gpu": (_i, [_vp, _i, _i]),
     "bluestein_fft_gpu": (_i, [_vp, _i, _i]), "fft_mixed_radix_gpu": (_i, [_vp, _i, _i]),
 }
+
+# declared in include/fft_apps.h under the reference's own name, which none of the prefixes of SIGNATURES' names covers
+EXTRA_SIGNATURES = {"compute_coherence_gpu": (_vp, [_vp, _vp, _i, _i])}
 
 _lib = None
 
@@ -127,7 +137,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("HIP extension missing: %s (build it: make -C %s)" % (LIB_PATH, HERE))
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXTRA_SIGNATURES.items()):
             f = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             f.restype = res
             f.argtypes = args
@@ -280,6 +290,7 @@ class Plan:
 FUSED_KINDS = {"conv": 0, "circ": 1, "autocorr": 2, "xcorr": 3, "psd": 4}
 WINDOWS = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3, "user": 4}
 FRAMES_OUT = {"stft": 0, "power": 1, "welch": 2}
+CROSS_OUT = {"csd": 0, "coherence": 1, "transfer": 2, "all": 3}
 
 
 class ExtPlan:
@@ -363,6 +374,43 @@ class ExtPlan:
         p.out_len = p.lib.fft_gpu_iframes_len_hip(p.handle)
         p.unrecoverable = p.lib.fft_gpu_iframes_unrecoverable_hip(p.handle)
         return p
+
+    @classmethod
+    def cross_frames(cls, n, hop, signal_len, n_signals=1, window="hann", out="csd", dtype=np.float64):
+        """Cross-spectral density ("csd"), magnitude-squared coherence, H1 transfer estimate or all three spectra ("all") of n_signals
+        PAIRS of signals on overlapping frames (fft_gpu_plan_cross_frames_real_hip for float32 / float64 signals,
+        fft_gpu_plan_cross_frames_hip for complex64 / complex128).  window: a name of WINDOWS, or n real values (USER).
+        chunk: the frames per chunk of the reduction."""
+        dt = np.dtype(dtype)
+        real = dt in (np.dtype(np.float32), np.dtype(np.float64))
+        f32 = dt in (np.dtype(np.complex64), np.dtype(np.float32))
+        w = None
+        if not isinstance(window, str):
+            w = np.ascontiguousarray(np.asarray(window).astype(np.float32 if f32 else np.float64))
+            if w.shape != (n,):
+                raise ValueError("a user window has n values")
+        lib = init()
+        make = lib.fft_gpu_plan_cross_frames_real_hip if real else lib.fft_gpu_plan_cross_frames_hip
+        p = cls(make(n, hop, signal_len, n_signals, WINDOWS["user" if w is not None else window],
+                     None if w is None else w.ctypes.data, CROSS_OUT[out], PREC_F32 if f32 else PREC_F64))
+        p.n, p.n_signals, p.out, p.dtype, p.real = n, n_signals, out, dt, real
+        p.nw = p.lib.fft_gpu_frames_count_hip(p.handle)
+        p.chunk = p.lib.fft_gpu_cross_chunk_hip(p.handle)
+        return p
+
+    def cross_out(self):
+        """(shape, dtype) of a cross frames plan's result."""
+        f32 = self.dtype in (np.dtype(np.complex64), np.dtype(np.float32))
+        hb = self.n // 2 + 1
+        if self.out == "coherence":
+            return (self.n_signals, hb), np.dtype(np.float32 if f32 else np.float64)
+        if self.out == "all":
+            return (self.n_signals, hb, 4), np.dtype(np.float32 if f32 else np.float64)
+        return (self.n_signals, hb), np.dtype(np.complex64 if f32 else np.complex128)
+
+    def execute_cross(self, d_x, d_y, d_out, x_pitch=0, y_pitch=0, sample_rate=1.0):
+        if self.lib.fft_gpu_execute_cross_frames_hip(self.handle, d_x, x_pitch, d_y, y_pitch, d_out, sample_rate) != 0:
+            raise RuntimeError("fft_gpu_execute_cross_frames_hip failed")
 
     def execute_iframes(self, d_X, d_y, signal_pitch=0):
         if self.lib.fft_gpu_execute_iframes_hip(self.handle, d_X, d_y, signal_pitch) != 0:
@@ -539,6 +587,43 @@ def spectrogram(x, n, hop, window="hann", fs=1.0):
 def welch(x, n, hop, window="hann", fs=1.0):
     """-> [signals, n//2 + 1] real: Welch's PSD, the mean of the frames' periodograms."""
     return _frames(x, n, hop, window, "welch", fs)
+
+
+def _cross(x, y, n, hop, window, out, fs):
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    if x.shape != y.shape or x.dtype != y.dtype:
+        raise ValueError("x and y have one shape and one dtype")
+    x2, y2 = (x.reshape(1, -1), y.reshape(1, -1)) if x.ndim == 1 else (x, y)
+    plan = ExtPlan.cross_frames(n, hop, x2.shape[1], x2.shape[0], window, out, x2.dtype)
+    shape, odt = plan.cross_out()
+    a, b, o = DeviceBuffer(x2.nbytes), DeviceBuffer(y2.nbytes), DeviceBuffer(int(np.prod(shape)) * odt.itemsize)
+    a.upload(x2)
+    b.upload(y2)
+    plan.execute_cross(a.ptr, b.ptr, o.ptr, 0, 0, fs)
+    if plan.sync() != 0:
+        raise RuntimeError("execute failed")
+    res = o.download(shape, odt)
+    for buf in (a, b, o):
+        buf.free()
+    plan.destroy()
+    return res[0] if x.ndim == 1 else res
+
+
+def csd(x, y, n, hop, window="hann", fs=1.0):
+    """x, y: [signals, len] (or [len]) float32 / float64 (real signals, read where they lie) or complex64 / complex128
+    -> [signals, n//2 + 1] complex: the cross-spectral density Pxy = c_k mean_w conj(X_w) Y_w over the frames of stft()
+    (scipy.signal.csd's convention and scaling, without detrending)."""
+    return _cross(x, y, n, hop, window, "csd", fs)
+
+
+def coherence(x, y, n, hop, window="hann"):
+    """-> [signals, n//2 + 1] real: the magnitude-squared coherence |Pxy|^2 / (Pxx Pyy); 0 where Pxx Pyy is 0."""
+    return _cross(x, y, n, hop, window, "coherence", 1.0)
+
+
+def transfer(x, y, n, hop, window="hann"):
+    """-> [signals, n//2 + 1] complex: the H1 transfer estimate Pxy / Pxx from x to y; 0 where Pxx is 0."""
+    return _cross(x, y, n, hop, window, "transfer", 1.0)
 
 
 def fft(x, direction=FFT_FORWARD, algo=ALGO_AUTO, inplace=True):

@@ -144,3 +144,57 @@ double* fft_welch_psd_real_gpu(const double* signal, int signal_len, double samp
     }
     return psd;
 }
+
+/* plan, upload both signals, execute, download: one pair through a cross frames plan (elem_bytes: 8 real, 16 complex samples) */
+static int run_cross(int real_input, const void* x, const void* y, int n, double sample_rate, int window_size, int overlap, fft_gpu_cross_out_t kind,
+                     void* out, size_t out_bytes) {
+    if (!x || !y || !out || window_size < (real_input ? 4 : 2) || !is_power_of_two(window_size) || overlap < 0 || overlap >= window_size ||
+        n < window_size) {
+        fprintf(stderr, "Error: cross spectra need a power-of-two window_size >= %d, 0 <= overlap < window_size <= n\n", real_input ? 4 : 2);
+        return -1;
+    }
+    if (ensure_gpu() != 0) return -1;
+    const size_t in_bytes = (size_t)n * (real_input ? sizeof(double) : sizeof(complex_t));
+    int rc = -1;
+    fft_gpu_plan_t plan = real_input ? fft_gpu_plan_cross_frames_real_hip(window_size, window_size - overlap, n, 1, FFT_GPU_WINDOW_HANN, NULL, kind, FFT_PREC_F64)
+                                     : fft_gpu_plan_cross_frames_hip(window_size, window_size - overlap, n, 1, FFT_GPU_WINDOW_HANN, NULL, kind, FFT_PREC_F64);
+    fft_gpu_memory_t dx = plan ? fft_gpu_alloc_bytes_hip(in_bytes) : NULL;
+    fft_gpu_memory_t dy = plan ? fft_gpu_alloc_bytes_hip(in_bytes) : NULL;
+    fft_gpu_memory_t dout = plan ? fft_gpu_alloc_bytes_hip(out_bytes) : NULL;
+    if (plan && dx && dy && dout) {
+        if (fft_gpu_copy_h2d_bytes_hip(dx, x, in_bytes) == 0 && fft_gpu_copy_h2d_bytes_hip(dy, y, in_bytes) == 0 &&
+            fft_gpu_execute_cross_frames_hip(plan, fft_gpu_memory_ptr(dx), 0, fft_gpu_memory_ptr(dy), 0, fft_gpu_memory_ptr(dout), sample_rate) == 0 &&
+            fft_gpu_plan_sync(plan) == 0 && fft_gpu_copy_d2h_bytes_hip(out, dout, out_bytes) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(dx);
+    fft_gpu_free(dy);
+    fft_gpu_free(dout);
+    fft_gpu_destroy_plan(plan);
+    return rc;
+}
+
+static double* coherence_of(int real_input, const void* x, const void* y, int n, int window_size, int overlap) {
+    if (window_size < 2) return NULL;
+    const size_t bytes = ((size_t)window_size / 2 + 1) * sizeof(double);
+    double* coh = (double*)malloc(bytes);
+    if (!coh) return NULL;
+    if (run_cross(real_input, x, y, n, 1.0, window_size, overlap, FFT_GPU_CROSS_COHERENCE, coh, bytes) != 0) {
+        free(coh);
+        return NULL;
+    }
+    return coh;
+}
+
+double* compute_coherence_gpu(const complex_t* x, const complex_t* y, int n, int window_size) {
+    return coherence_of(0, x, y, n, window_size, window_size / 2);
+}
+
+double* fft_coherence_real_gpu(const double* x, const double* y, int n, int window_size, int overlap) {
+    return coherence_of(1, x, y, n, window_size, overlap);
+}
+
+int fft_csd_real_gpu(const double* x, const double* y, int n, double sample_rate, int window_size, int overlap, complex_t* pxy) {
+    if (window_size < 4) return -1;
+    return run_cross(1, x, y, n, sample_rate, window_size, overlap, FFT_GPU_CROSS_CSD, pxy, ((size_t)window_size / 2 + 1) * sizeof(complex_t));
+}

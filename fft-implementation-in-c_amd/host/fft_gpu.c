@@ -222,6 +222,27 @@ int fft_gpu_execute_iframes(fft_gpu_plan_t plan, const void* d_X, void* d_y, lon
     return fft_gpu_execute_iframes_hip(plan, d_X, d_y, signal_pitch);
 }
 
+/* cross frames plans: cross-spectral density, coherence and transfer estimate of signal pairs */
+fft_gpu_plan_t fft_gpu_plan_cross_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                         fft_gpu_cross_out_t out, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_cross_frames")) return NULL;
+    return fft_gpu_plan_cross_frames_hip(n, hop, signal_len, n_signals, window, w_host, out, prec);
+}
+
+fft_gpu_plan_t fft_gpu_plan_cross_frames_real(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                              fft_gpu_cross_out_t out, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_cross_frames_real")) return NULL;
+    return fft_gpu_plan_cross_frames_real_hip(n, hop, signal_len, n_signals, window, w_host, out, prec);
+}
+
+int fft_gpu_cross_chunk(fft_gpu_plan_t plan) { return fft_gpu_cross_chunk_hip(plan); }
+
+int fft_gpu_execute_cross_frames(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch, void* d_out,
+                                 double sample_rate) {
+    if (!backend_is_hip("fft_gpu_execute_cross_frames")) return -1;
+    return fft_gpu_execute_cross_frames_hip(plan, d_x, x_pitch, d_y, y_pitch, d_out, sample_rate);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

@@ -38,6 +38,18 @@ double* fft_welch_psd_gpu(const complex_t* signal, int signal_len, double sample
 /* The same for a REAL signal (window_size a power of two >= 4): ONE real frames plan (fft_gpu_plan_frames_real_hip) reads the doubles
  * in place on the device, no complex copy of the signal is made anywhere. */
 double* fft_welch_psd_real_gpu(const double* signal, int signal_len, double sample_rate, int window_size, int overlap);
+/* Magnitude-squared coherence of two signals of n samples (compute_coherence, applications/power_spectrum.c:195-224: its signature,
+ * its Hann window, overlap window_size / 2 and rate 1 -- and the coherence itself, |Pxy|^2 / (Pxx Pyy), where the reference writes a
+ * placeholder of 1.0 for want of a cross spectrum; 0 where Pxx Pyy is not > 0, its own rule).  window_size a power of two >= 2,
+ * <= n.  A malloc'd array of window_size/2 + 1 doubles freed by the caller; NULL on failure.  ONE cross frames plan
+ * (fft_gpu_plan_cross_frames_hip). */
+double* compute_coherence_gpu(const complex_t* x, const complex_t* y, int n, int window_size);
+/* The same for REAL signals with a free overlap, 0 <= overlap < window_size (a power of two >= 4) <= n: ONE real cross frames plan
+ * (fft_gpu_plan_cross_frames_real_hip), no complex copy of the signals. */
+double* fft_coherence_real_gpu(const double* x, const double* y, int n, int window_size, int overlap);
+/* Cross-spectral density Pxy = c_k mean_w conj(X_w) Y_w of two real signals (scipy's csd convention): pxy has room for
+ * window_size/2 + 1 values.  0 / -1. */
+int fft_csd_real_gpu(const double* x, const double* y, int n, double sample_rate, int window_size, int overlap, complex_t* pxy);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,14 @@ typedef enum { FFT_GPU_WINDOW_RECT = 0, FFT_GPU_WINDOW_HANN = 1, FFT_GPU_WINDOW_
 typedef enum { FFT_GPU_FRAMES_STFT = 0,    /* [S][nw][n] complex, unscaled */
                FFT_GPU_FRAMES_POWER = 1,   /* [S][nw][n/2 + 1] real: one periodogram per frame */
                FFT_GPU_FRAMES_WELCH = 2 }  /* [S][n/2 + 1] real: their mean over the frames */ fft_gpu_frames_out_t;
+/* Two-signal statistics on the same frames (scipy's csd / coherence; what the reference's compute_coherence,
+ * applications/power_spectrum.c:195-224, leaves as a placeholder): with X_w, Y_w the STFT rows of frame w of a pair (x, y),
+ *     Pxx[k] = c_k mean_w |X_w[k]|^2,   Pyy[k] = c_k mean_w |Y_w[k]|^2,   Pxy[k] = c_k mean_w conj(X_w[k]) Y_w[k],
+ * c_k = 1 / (sample_rate * P), doubled for 0 < k < n/2 (the POWER / WELCH scaling); hb = n/2 + 1 bins per pair. */
+typedef enum { FFT_GPU_CROSS_CSD = 0,        /* [S][hb] complex: Pxy */
+               FFT_GPU_CROSS_COHERENCE = 1,  /* [S][hb] real: |Pxy|^2 / (Pxx Pyy); exactly 0 where Pxx Pyy is not > 0 (power_spectrum.c:213-217) */
+               FFT_GPU_CROSS_TRANSFER = 2,   /* [S][hb] complex: H1 = Pxy / Pxx; exactly (0, 0) where Pxx is not > 0 */
+               FFT_GPU_CROSS_ALL = 3 }       /* [S][hb][4] reals: Pxx, Pyy, Re Pxy, Im Pxy */ fft_gpu_cross_out_t;
 
 /* backend-level additive entry points */
 int fft_gpu_device_count_hip(void);
@@ -249,6 +257,28 @@ int fft_gpu_iframes_unrecoverable_hip(fft_gpu_plan_t plan);  /* samples per sign
  * < out_len: -1); the signal_pitch - out_len reals between signals are never touched.  NULL pointers and d_X == d_y return -1;
  * nothing is launched then. */
 int fft_gpu_execute_iframes_hip(fft_gpu_plan_t plan, const void* d_X, void* d_y, long long signal_pitch /* 0: out_len */);
+/* Cross-spectral density, magnitude-squared coherence and H1 transfer estimate of n_signals PAIRS of signals of signal_len samples
+ * (see fft_gpu_cross_out_t; the kind is fixed at plan time).  n, hop, signal_len, n_signals, window, w_host, nw and the limits are
+ * those of fft_gpu_plan_frames_hip (complex signals, n >= 2) and fft_gpu_plan_frames_real_hip (real signals, n >= 4); anything else,
+ * a bad kind or a failed allocation returns NULL.  The plan owns one frames plan in STFT mode, used unchanged -- its one-launch path
+ * where it has one, its fallback where not or under FFT_GPU_OPT_NO_FUSION -- and runs it on x and on y into two row workspaces
+ * allocated at plan time ([S * nw][n/2 + 1] complex for real signals, [S * nw][n] for complex ones, of which bins 0 .. n/2 are
+ * read).  Two kernels reduce them: one thread per (pair, chunk of C frames, bin) sums |X|^2, |Y|^2 and conj(X) Y in double, frames
+ * ascending; one thread per (pair, bin) sums the chunks ascending in double, scales by c_k / nw, forms the output kind in double and
+ * rounds once.  No atomics: bit-reproducible, independent of the launch geometry; C is a function of (nw, n_signals, n) alone
+ * (fft_gpu_cross_chunk_hip).  A zero-power bin gives 0 as stated above (a NaN is not zero power: it propagates to its pair's rows
+ * and to no other pair's).  fft_gpu_plan_info_hip: n, batch = n_signals * nw, the inner core's passes, fused = the inner plan's,
+ * chunk_batch = C.  fft_gpu_frames_count_hip, set_stream, sync, set_option and destroy as for frames plans. */
+fft_gpu_plan_t fft_gpu_plan_cross_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window,
+                                             const void* w_host /* n reals of prec, USER only */, fft_gpu_cross_out_t out, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_cross_frames_real_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window,
+                                                  const void* w_host /* n reals of prec, USER only */, fft_gpu_cross_out_t out, fft_precision_t prec);
+int fft_gpu_cross_chunk_hip(fft_gpu_plan_t plan);    /* C, frames per chunk of the reduction; -1: not a cross frames plan */
+/* async on the plan's stream.  d_x, d_y: the two signals of every pair, pair s at d_x + s * x_pitch and d_y + s * y_pitch elements
+ * (reals for a real plan; 0: signal_len; < signal_len: -1).  d_x == d_y is legal.  d_out must overlap neither input.  NULL
+ * pointers, short pitches and an overlapping output return -1; nothing is launched then. */
+int fft_gpu_execute_cross_frames_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch,
+                                     void* d_out, double sample_rate);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
@@ -329,6 +359,14 @@ fft_gpu_plan_t fft_gpu_plan_iframes_real(int n, int hop, int n_frames, int n_sig
 int fft_gpu_iframes_len(fft_gpu_plan_t plan);
 int fft_gpu_iframes_unrecoverable(fft_gpu_plan_t plan);
 int fft_gpu_execute_iframes(fft_gpu_plan_t plan, const void* d_X, void* d_y, long long signal_pitch);
+/* cross frames plans (fft_gpu_plan_cross_frames_hip above) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_cross_frames(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                         fft_gpu_cross_out_t out, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_cross_frames_real(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
+                                              fft_gpu_cross_out_t out, fft_precision_t prec);
+int fft_gpu_cross_chunk(fft_gpu_plan_t plan);
+int fft_gpu_execute_cross_frames(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch, void* d_out,
+                                 double sample_rate);
 
 #ifdef __cplusplus
 }
