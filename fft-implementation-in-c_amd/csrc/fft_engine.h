@@ -50,6 +50,7 @@
 
 #include "fft_kernels.h"
 #include "fft_kernels_chain.h"
+#include "fft_rows_list.h"
 #include "fft_team_list.h"
 #include "fft_team_defer.h"
 #include "fft_mixed_radix.h"
@@ -105,6 +106,15 @@ struct ExecHooks {
     // in + f * (n + 1); pre_tab = W_2n^k (k <= n, shared) is the c2r merge's table, and the rows that leave are the frames' 2 n real
     // samples read as n complex values (TileHooks, HOOK bit 7)
     bool herm_rows = false;
+    // single-pass plans only (execute_filter): overlap-save filtering.  The transforms of the execute are the blocks of signals, block
+    // w of a signal starting frame_lead samples before its sample w * in_pitch (in_pitch = B, the block advance); samples outside
+    // [0, signal_len) read as zero.  mid_tab = the filter's spectrum; of every block's result the values l >= frame_lead go to
+    // out + sig * out_signal_pitch + (w * B + l - frame_lead - out_off), inside [0, out_len) only (TileHooks, HOOK bits 8 and 9)
+    bool filter = false;
+    int frame_lead = 0;
+    long long signal_len = 0;
+    long long out_signal_pitch = 0;
+    long long out_len = 0, out_off = 0;
 };
 
 enum Algo { ALGO_AUTO = 0, ALGO_RADIX2 = 1, ALGO_RADIX4 = 2, ALGO_SPLIT_RADIX = 3, ALGO_RADIX2_GLOBAL = 4, ALGO_BLUESTEIN = 5, ALGO_RADIX2_SHFL = 6, ALGO_MIXED_RADIX = 7 };
@@ -1286,6 +1296,26 @@ class Pow2Plan {
         if (side & 4) {  // FFT -> mid product -> inverse FFT in this one launch (single-pass plans: execute_round)
             k.mid_tab = h.mid_tab;
             k.mid_mode = (h.mid_tab || h.mid_mode == HOOK_ABS2) ? h.mid_mode : HOOK_NONE;
+            if (h.filter) {  // overlap-save blocks (execute_filter): bounded framed load, round trip, valid-part framed store
+                if (hook_kind(p) != 1 || side != (3 | 4) || h.frames_per_signal < 1) return;
+                k.pre_tab = nullptr; k.pre_mode = HOOK_NONE;
+                k.post_tab = nullptr; k.post_mode = HOOK_NONE;
+                k.n_in = (int)n; k.n_out = (int)n;
+                k.frames_per_signal = h.frames_per_signal;
+                k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
+                k.signal_pitch = h.signal_pitch;
+                k.frame_lead = h.frame_lead;
+                k.signal_len = (int)h.signal_len;
+                k.out_signal_pitch = h.out_signal_pitch;
+                k.out_len = (int)h.out_len;
+                k.out_off = (int)h.out_off;
+                // base and pitch aligned; the kernel decides chunk by chunk from the sample position
+                k.in_vec_ok = ((h.signal_pitch % V) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+                k.out_vec_ok = ((h.out_signal_pitch % V) == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+                tp.nt &= ~1;  // blocks always overlap: their lines are asked for again
+                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, FFT_ROWS_FILTER_HOOK>, tp, -1, p);
+                return;
+            }
             if (hook_kind(p) == 1) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 8>, tp, -1, p);
             return;
         }
@@ -1366,6 +1396,16 @@ class Pow2Plan {
     void execute_frames(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
         run_if = nullptr;
         launch_pass_hooked(0, in, out, nf, false, (T)1, h, 3, 0);
+        rt->mark(0);
+    }
+
+    // ---- single-pass sizes: overlap-save filtering (ExecHooks::filter) -- the nf transforms of ONE launch are the overlapping blocks of
+    // signals, multiplied by h.mid_tab between the forward and the inverse transform, and only the valid part of every block is
+    // stored, straight into the output signals.  Requires round_capable() and frames_exact(nf, frames_per_signal).
+    void execute_filter(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
+        const long long n = 1ll << log2n;
+        run_if = nullptr;
+        launch_pass_hooked(0, in, out, nf, false, (T)(1.0L / (long double)n), h, 3 | 4, 0);
         rt->mark(0);
     }
 

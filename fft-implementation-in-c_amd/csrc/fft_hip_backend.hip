@@ -38,6 +38,10 @@ FFT_ROWS_FIXED_LIST(FFT_EXTERN_FIXED)
     extern template __global__ void tile_fft_kernel<T, 8, 1, FAM_SR16, LOAD_LCONTIG, STORE_LCONTIG, false, ((LOG2L) << 8) | (LOG2C)>(TileParams<T>);
 FFT_ROWS_FIXED8_LIST(FFT_EXTERN_FIXED8)
 #undef FFT_EXTERN_FIXED8
+#define FFT_EXTERN_FILTER(T) \
+    extern template __global__ void tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, FFT_ROWS_FILTER_HOOK>(TileParams<T>);
+FFT_ROWS_FILTER_LIST(FFT_EXTERN_FILTER)
+#undef FFT_EXTERN_FILTER
 }  // namespace fftk
 
 // the exchange protocol of team_quad_kernel by size (team_quad_slots): 3 = one image per seat + the pair protocol where it measured faster than
@@ -307,7 +311,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -321,9 +325,11 @@ struct fft_gpu_plan {
     ffteng::IFramesPlan<double, HipRT>* i64 = nullptr;
     ffteng::CrossFramesPlan<float, HipRT>* x32 = nullptr;  // cross-spectral density / coherence / transfer estimate on the frames of signal pairs
     ffteng::CrossFramesPlan<double, HipRT>* x64 = nullptr;
+    ffteng::FilterPlan<float, HipRT>* s32 = nullptr;  // overlap-save FIR filtering of long signals
+    ffteng::FilterPlan<double, HipRT>* s64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8 };
 
 namespace {
 
@@ -431,6 +437,8 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
     if (p->i64) f(&p->i64->core);
     if (p->x32) f(&p->x32->inner.core);
     if (p->x64) f(&p->x64->inner.core);
+    if (p->s32) f(&p->s32->core);
+    if (p->s64) f(&p->s64->core);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -486,6 +494,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->w32 || p->w64) return -1;  // frames plans take a signal pitch and a sample rate: fft_gpu_execute_frames_hip
     else if (p->i32 || p->i64) return -1;  // inverse frames plans take a signal pitch: fft_gpu_execute_iframes_hip
     else if (p->x32 || p->x64) return -1;  // cross frames plans take two signals: fft_gpu_execute_cross_frames_hip
+    else if (p->s32 || p->s64) return -1;  // filter plans take two pitches: fft_gpu_execute_filter_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -752,6 +761,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->i64;
         delete p->x32;
         delete p->x64;
+        delete p->s32;
+        delete p->s64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -1061,6 +1072,54 @@ int fft_gpu_execute_cross_frames_hip(fft_gpu_plan_t p, const void* d_x, long lon
     return 0;
 }
 
+// Overlap-save FIR filtering (fft_plans_ext.h FilterPlan); h_host: n_taps complex taps of `prec` in host memory
+fft_gpu_plan_t fft_gpu_plan_filter_hip(int n_taps, const void* h_host, int signal_len, int n_signals, int n, fft_gpu_filter_out_t out, fft_precision_t prec) {
+    if (n_taps < 1 || !h_host || signal_len < 1 || n_signals < 1 || n < 0 || (n & (n - 1)) != 0 || (n > 0 && n <= n_taps - 1) || (int)out < 0 || (int)out > 2) {
+        fprintf(stderr, "fft_hip: invalid filter plan arguments (taps=%d signal_len=%d signals=%d n=%d out=%d)\n", n_taps, signal_len, n_signals, n, (int)out);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(n, n_signals, -1, prec, PLAN_FILTER);
+    if (!p) return NULL;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->s32 = new (std::nothrow) ffteng::FilterPlan<float, HipRT>();
+        ok = p->s32 && p->s32->build(&p->rt, n_taps, (const fftk::cpx<float>*)h_host, signal_len, n_signals, n, (int)out);
+        if (ok) { p->n = p->s32->n; p->batch = (int)p->s32->blocks(); }
+    } else {
+        p->s64 = new (std::nothrow) ffteng::FilterPlan<double, HipRT>();
+        ok = p->s64 && p->s64->build(&p->rt, n_taps, (const fftk::cpx<double>*)h_host, signal_len, n_signals, n, (int)out);
+        if (ok) { p->n = p->s64->n; p->batch = (int)p->s64->blocks(); }
+    }
+    return finish_plan(p, ok, "filter");
+}
+int fft_gpu_filter_out_len_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->s32) return p->s32->out_len;
+    if (p->s64) return p->s64->out_len;
+    return -1;
+}
+int fft_gpu_filter_block_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->s32) return p->s32->n;
+    if (p->s64) return p->s64->n;
+    return -1;
+}
+// async on the plan's stream.  d_x: the signals, x_pitch elements apart (0: signal_len); d_y: the outputs, y_pitch apart (0: out_len);
+// the two must not overlap
+int fft_gpu_execute_filter_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
+    if (!p || !d_x || !d_y || (!p->s32 && !p->s64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->s32 ? p->s32->execute((const fftk::cpx<float>*)d_x, x_pitch, (fftk::cpx<float>*)d_y, y_pitch)
+                          : p->s64->execute((const fftk::cpx<double>*)d_x, x_pitch, (fftk::cpx<double>*)d_y, y_pitch);
+    if (rc != 0) return -1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
 int fft_gpu_plan_set_stream_hip(fft_gpu_plan_t p, void* hip_stream) {
     if (!p) return -1;
     (void)hipStreamSynchronize(p->rt.stream);
@@ -1305,15 +1364,17 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->i64) p->i64->no_fusion = value != 0;
             if (p->x32) p->x32->inner.no_fusion = value != 0;
             if (p->x64) p->x64->inner.no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64) ? 0 : -1;
+            if (p->s32) p->s32->no_fusion = value != 0;
+            if (p->s64) p->s64->no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
                 q->no_chain = value == 1;
                 q->core.chain_min_log2n = value == 2 ? 0 : std::remove_reference_t<decltype(q->core)>::kChainMinLog2n;
             };
-            set(p->b32); set(p->b64); set(p->f32); set(p->f64);
-            return (p->b32 || p->b64 || p->f32 || p->f64) ? 0 : -1;
+            set(p->b32); set(p->b64); set(p->f32); set(p->f64); set(p->s32); set(p->s64);
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->s32 || p->s64) ? 0 : -1;
         }
         default:
             return -1;
@@ -1469,6 +1530,13 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->x32) fill_cross(p->x32);
     if (p->x64) fill_cross(p->x64);
+    auto fill_filter = [&](auto* f) {  // n = the block length, batch = signals * blocks, the core's passes; fused: 3 the one-launch path, else the fallback's middle
+        fill(&f->core);
+        info->fused = f->path();
+        if (f->work) info->workspace_bytes += (size_t)2 * (size_t)f->chunk_blocks * (size_t)f->n * sizeof(*f->work);
+    };
+    if (p->s32) fill_filter(p->s32);
+    if (p->s64) fill_filter(p->s64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

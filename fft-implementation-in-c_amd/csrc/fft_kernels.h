@@ -115,6 +115,20 @@ struct TileHooks {
     // mirrored bin X[L-k] is read from the frame's own LDS row once the tile has landed.  pre_mode is HOOK_NONE: pre_tab is the
     // merge's table, not a factor.  With inverse = 1 and scale = 1 / L the column that leaves is the frame's 2L real samples.
     // Rows of L + 1 bins start only sizeof(cpx<T>)-aligned: in_vec_ok is 0 in fp32 (value-by-value loads).
+    // HOOK bit 8 (single-pass kernel only, with bits 0 and 4): BOUNDED framed load, the input side of overlap-save filtering.  Block
+    // (sig, w) of bit 4's split starts frame_lead samples BEFORE sample w * in_c of its signal: sample l of the block is the signal's
+    // sample q = w * in_c - frame_lead + l (long long), read only if 0 <= q < signal_len and zero otherwise -- memory outside the
+    // signal is never touched.  16-byte loads only for chunks wholly inside [0, signal_len) at a 16-byte aligned address (in_vec_ok
+    // then says: base and pitch are aligned); everything else value by value.  No load-side table (pre_mode = HOOK_NONE).
+    int frame_lead;
+    int signal_len;
+    // HOOK bit 9 (single-pass kernel only, with bits 1, 4 and 8): VALID-PART framed store.  Value l of block (sig, w) goes to
+    // out + sig * out_signal_pitch + p, p = w * in_c + l - frame_lead - out_off, only if l >= frame_lead and 0 <= p < out_len: the
+    // first frame_lead values of every block (the circular wrap) are dropped, the rest lands in the output signal where it belongs.
+    // 16-byte stores only where the destination chunk is aligned and wholly valid (out_vec_ok: base and pitch aligned).
+    long long out_signal_pitch;
+    int out_len;
+    int out_off;
 };
 
 template <typename T>
@@ -504,7 +518,8 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 // product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store, bit 6 real frames: packed real load and
 // the r2c split in the store, bit 7 Hermitian rows load: one-sided rows in, the c2r merge on the way to the stages (TileHooks;
 // the last five on the hooked single-pass rows kernel only, bit 6 only with bits 0, 1 and 4, bit 7 with bit 0 and none of bits
-// 2 to 6).  Compile-time bits: an instantiation without one compiles to the code it had before.
+// 2 to 6), bit 8 bounded framed load and bit 9 valid-part framed store: overlap-save filtering, with bits 0, 1, 3 and 4 and none of the
+// others.  Compile-time bits: an instantiation without one compiles to the code it had before.
 // waves per SIMD the register budget of an instantiation is sized for.  The fp32 kernels with their shape baked in need only
 // 92-122 VGPRs when built for four waves per SIMD (no spills; built for two they take 150-250 because they may), i.e. two
 // 512-thread workgroups per CU.  Measured (profiles/r2_ab_rows_fixed.txt): the single-pass rows kernel gains 5...12 % from
@@ -585,6 +600,11 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
     static_assert(!HK_HERM || (E == 4 && FAM == FAM_R4 && LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && H == 1 && !TWIDDLE && HK_LOAD &&
                                !(HOOK & (4 | 8 | 16 | 32 | 64))),
                   "Hermitian rows load: on the hooked single-pass rows kernel only, with the load side and none of bits 2 to 6");
+    constexpr bool HK_BOUND = (HOOK & 256) != 0, HK_VALID = (HOOK & 512) != 0;  // TileHooks: bounded framed load, valid-part framed store
+    static_assert(!(HK_BOUND || HK_VALID) || (E == 4 && H == 1 && FAM == FAM_R4 && LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && !TWIDDLE &&
+                                              FIXED == 0 && HK_LOAD && HK_FRAMES && !(HOOK & (4 | 32 | 64 | 128))),
+                  "bounded framed load / valid-part store: on the hooked single-pass rows kernel only, with the framed load and none of bits 2, 5, 6, 7");
+    static_assert(!HK_VALID || (HK_BOUND && HK_STORE), "valid-part framed store: with the store side and the bounded framed load");
     vec16<T> nxttab[HK_TABPF ? DEPTH : 1][HK_TABPF ? H : 1][HK_TABPF ? E : 1];  // the load-side table values of the same chunks
     const bool pre_on = HK_LOAD && p.hk.pre_mode != HOOK_NONE;  // wave-uniform
     // index (inside its transform) of the first sample of lane-load i of group h, and its tile column / row
@@ -609,6 +629,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                 bool live;
                 const cpx<T>* src;
                 const T* rsrc = nullptr;  // HK_REAL: the chunk's first real sample (an address that may be only sizeof(T)-aligned)
+                long long q0 = 0;         // HK_BOUND: the chunk's first sample, counted inside its signal (src = the signal's sample 0)
                 if (LOADM == LOAD_CCONTIG) {
                     const long long l = r + ((long long)i << log2TPC);
                     live = (tc.c0 + h * CG + V * j) < p.n_cols;
@@ -623,7 +644,10 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     if (HK_FRAMES) {  // frame f of the execute: signal f / frames_per_signal, frame f % frames_per_signal inside it
                         const unsigned f = (unsigned)(tc.c0 + t), fps = (unsigned)p.hk.frames_per_signal;
                         const unsigned sig = fps == 1u ? f : (unsigned)(((unsigned long long)f * p.hk.frames_rcp) >> 32);
-                        if (HK_REAL) {  // hop and pitch count REAL samples; sample pair l0 of the frame is its reals 2 l0, 2 l0 + 1
+                        if (HK_BOUND) {  // block w of signal sig: its chunk starts at sample q0 of the signal, which may lie outside it
+                            src = p.in + (long long)sig * p.hk.signal_pitch;
+                            q0 = (long long)(f - sig * fps) * p.in_c - p.hk.frame_lead + l0;
+                        } else if (HK_REAL) {  // hop and pitch count REAL samples; sample pair l0 of the frame is its reals 2 l0, 2 l0 + 1
                             rsrc = reinterpret_cast<const T*>(p.in) + (long long)sig * p.hk.signal_pitch + (long long)(f - sig * fps) * p.in_c + 2 * l0;
                             src = nullptr;
                         } else {
@@ -639,7 +663,18 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                     FFT_UNROLL
                     for (int vv = 0; vv < V; vv++) nxt[h][i].c[vv] = mk<T>((T)0, (T)0);
                     if (live && idx0 < n_in) {
-                        if (HK_REAL) {
+                        if (HK_BOUND) {
+                            // samples outside [0, signal_len) are zero and never read; a 16-byte load only for a chunk wholly inside
+                            // at an aligned address (base and pitch aligned: the address is aligned where q0 is a multiple of V)
+                            const long long slen = p.hk.signal_len;
+                            if (p.hk.in_vec_ok && q0 >= 0 && q0 + V <= slen && (q0 & (V - 1)) == 0) {
+                                nxt[h][i] = fft_ld16<0>(reinterpret_cast<const vec16<T>*>(src + q0));
+                            } else {
+                                FFT_UNROLL
+                                for (int vv = 0; vv < V; vv++)
+                                    if (q0 + vv >= 0 && q0 + vv < slen) nxt[h][i].c[vv] = src[q0 + vv];
+                            }
+                        } else if (HK_REAL) {
                             // in_vec_ok: every frame starts 16-byte aligned (base, hop and pitch), so does every chunk of it.  Otherwise
                             // component by component: no cpx<T> is read at an address that is not sizeof(cpx<T>)-aligned (odd hop)
                             if (p.hk.in_vec_ok) {
@@ -962,7 +997,29 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                         const int g = tid + i * nthreads;
                         const int t = h * CG + (g >> log2CPR);
                         const int pos = g & cpr_mask;
-                        if (HK_REAL) {
+                        if (HK_VALID) {
+                            // valid part of block (sig, w) = column c0 + t (TileHooks, bit 9): values l = pos * V ... go to sample
+                            // p0 ... of the signal's output.  Columns at or past n_cols store nothing; every store sits under
+                            // l >= frame_lead and 0 <= p < out_len, so no byte outside the out_len samples of a signal is written.
+                            const int l0 = pos * V, lead = p.hk.frame_lead;
+                            if (tc.c0 + t < p.n_cols && l0 + V > lead) {
+                                const unsigned f = (unsigned)(tc.c0 + t), fps = (unsigned)p.hk.frames_per_signal;
+                                const unsigned sig = fps == 1u ? f : (unsigned)(((unsigned long long)f * p.hk.frames_rcp) >> 32);
+                                const long long p0 = (long long)(f - sig * fps) * p.in_c + l0 - lead - p.hk.out_off;
+                                const long long olen = p.hk.out_len;
+                                if (p0 + V > 0 && p0 < olen) {
+                                    const vec16<T> v = *reinterpret_cast<const vec16<T>*>(smem + h * group_bytes + (size_t)(g >> log2CPR) * pitch + (size_t)pos * 16);
+                                    cpx<T>* orow = p.out + (long long)sig * p.hk.out_signal_pitch;
+                                    if (p.hk.out_vec_ok && l0 >= lead && p0 >= 0 && p0 + V <= olen && (p0 & (V - 1)) == 0) {
+                                        fft_st16<NTS>(reinterpret_cast<vec16<T>*>(orow + p0), v);
+                                    } else {
+                                        FFT_UNROLL
+                                        for (int vv = 0; vv < V; vv++)
+                                            if (l0 + vv >= lead && p0 + vv >= 0 && p0 + vv < olen) orow[p0 + vv] = v.c[vv];
+                                    }
+                                }
+                            }
+                        } else if (HK_REAL) {
                             // r2c split of frame c0 + t (TileHooks, bit 6): bins k = pos * V ... of its L + 1.  Z[k] is this thread's own chunk,
                             // Z[L - k] lies in the SAME LDS row, complete since the barrier above: no new barrier.  The pos == 0 thread also
                             // writes bin L.  Columns at or past n_cols -- the ragged last tile's, and a short batch's padding -- were loaded as

@@ -449,4 +449,40 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(512) copy_dma_kernel(const vec16<float>* in, v
 }
 #endif
 
+// ---------------------------------------------------------------------------
+// Overlap-save filtering, the unfused ends (FilterPlan's fallback; the fused kernel is tile_fft_kernel with HOOK bits 8 and 9 and
+// has the same predicates).  Block f = sig * nb + w of length n = 2^log2n holds the signal's samples q = w * B - lead + l, l < n,
+// zero where q lies outside [0, signal_len); of its circular convolution with the taps the values l >= lead are samples
+// p = w * B + l - lead - out_off of the signal's output, stored only for 0 <= p < out_len.  One thread per value; blocks
+// f0 ... f0 + total / n - 1 of the execute live in work[(f - f0) * n + l].
+// ---------------------------------------------------------------------------
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) filter_gather_kernel(const cpx<T>* x, long long x_pitch, int signal_len, int nb, int B, int lead, int log2n,
+                                                            long long f0, cpx<T>* work, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long f = f0 + (i >> log2n);
+        const int l = (int)(i & ((1ll << log2n) - 1));
+        const long long sig = f / nb;
+        const long long q = (f - sig * nb) * (long long)B - lead + l;
+        cpx<T> v = mk<T>((T)0, (T)0);
+        if (q >= 0 && q < signal_len) v = x[sig * x_pitch + q];
+        work[i] = v;
+    }
+}
+
+template <typename T>
+FFT_KERNEL void FFT_LAUNCH_BOUNDS(256) filter_scatter_kernel(const cpx<T>* work, cpx<T>* y, long long y_pitch, int out_len, int out_off, int nb, int B,
+                                                             int lead, int log2n, long long f0, long long total) {
+    const long long stride = FFT_NBLOCKS * FFT_NTHREADS;
+    for (long long i = FFT_BID * FFT_NTHREADS + FFT_TID; i < total; i += stride) {
+        const long long f = f0 + (i >> log2n);
+        const int l = (int)(i & ((1ll << log2n) - 1));
+        if (l < lead) continue;
+        const long long sig = f / nb;
+        const long long p = (f - sig * nb) * (long long)B + l - lead - out_off;
+        if (p >= 0 && p < out_len) y[sig * y_pitch + p] = work[i];
+    }
+}
+
 }  // namespace fftk

@@ -1,7 +1,7 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
-// overlapping frames, and the inverse STFT by overlap-add).  Templated on the same runtime policy RT as the engine, so the
+// overlapping frames, the inverse STFT by overlap-add, and overlap-save FIR filtering).  Templated on the same runtime policy RT as the engine, so the
 // unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
@@ -685,6 +685,159 @@ class IFramesPlan {
         const long long total = (long long)n_signals * out_len();
         launch_flat(rt, fftk::frames_overlap_add_kernel<T>, total, reinterpret_cast<const T*>(work), (const T*)win, (const T*)inv_env, y, signal_pitch, n, hop,
                     nw, out_len(), total);
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Overlap-save FIR filtering of long signals (reference applications/fft_filtering.c is the CPU consumer; its whole-signal mask is not
+// rebuilt): y = x * h for n_signals signals of signal_len samples and M = n_taps fixed taps, block by block.
+//   block length n (a power of two > M - 1), lead = M - 1, advance B = n - lead; block w of a signal holds its samples
+//   q = w B - lead + l, l < n (zero outside [0, signal_len)); of IFFT_n(FFT_n(block) . FFT_n(h)) the values l >= lead are the full
+//   convolution's samples w B ... w B + B - 1 (the first lead values are the circular wrap and are dropped);
+//   FULL     out_len = signal_len + M - 1, out_off = 0            np.convolve(x, h)
+//   CAUSAL   out_len = signal_len,         out_off = 0            y[t] = sum_j h[j] x[t - j]
+//   CENTRED  out_len = signal_len,         out_off = (M - 1) / 2  np.convolve(x, h, 'same')
+//   y[p] = full[p + out_off], p < out_len;  nb = ceil((out_off + out_len) / B) blocks per signal.
+// FFT_n(h) is computed once at plan time by the plan's own core.  Where n fits one hook-capable pass: ONE launch of the hooked
+// single-pass kernel over all n_signals * nb blocks (bounded framed load, spectral product and inverse on the registers, valid-part
+// framed store: tile_fft_kernel HOOK bits 8 and 9) -- one HBM round trip of the user's data, no [blocks][n] copy in or out.  Every
+// other n, a block count frames_exact() refuses, no_fusion and no_chain: filter_gather_kernel -> the core's forward . H . inverse
+// (one kernel, chained or hooked, as FusedPlan's circular convolution runs them) -> filter_scatter_kernel on chunks of blocks, so
+// the workspace stays bounded -- correct, not tuned.
+// n = 0: the plan chooses min(nmax, max(256, next_pow2(4 M))), nmax = 4096 (fp32) / 2048 (fp64); taps with M - 1 >= nmax / 2 get
+// next_pow2(4 M) on the fallback.  The rule is a guess, not a measurement.
+// ---------------------------------------------------------------------------
+enum FilterOut { FILTER_FULL = 0, FILTER_CAUSAL = 1, FILTER_CENTRED = 2 };
+
+template <typename T, typename RT>
+class FilterPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int kNmax = SZ == 8 ? 4096 : 2048;          // the largest block length one hooked pass holds
+    static constexpr long long kChunkElems = 1ll << 22;          // fallback: values per workspace (two of them)
+    RT* rt = nullptr;
+    int n_taps = 0, signal_len = 0, n_signals = 0, n = 0, B = 0, lead = 0, out_kind = 0, out_len = 0, out_off = 0, nb = 0;
+    Pow2Plan<T, RT> core;
+    cpx<T>* H = nullptr;       // FFT_n(h zero padded to n)
+    cpx<T>* work = nullptr;    // fallback: [chunk_blocks][n] gathered blocks, and [chunk_blocks][n] results behind them (allocated at its first use)
+    int chunk_blocks = 1;
+    bool ok = false;
+    bool no_fusion = false;
+    bool no_chain = false;
+    ~FilterPlan() {
+        if (!rt) return;
+        rt->dfree(H); rt->dfree(work);
+    }
+    long long blocks() const { return (long long)n_signals * nb; }
+    static int choose_n(int n_taps) {
+        long long want = 1;
+        while (want < 4ll * n_taps) want <<= 1;
+        if (n_taps - 1 >= kNmax / 2) return want > (1ll << 30) ? 0 : (int)want;
+        if (want < 256) want = 256;
+        return want > kNmax ? kNmax : (int)want;
+    }
+    bool hooked() const { return ok && !no_fusion && core.hook_capable(); }
+    // (n <= kNmax: a device whose LDS holds one pass of 4096 fp64 points still takes the fallback there -- the one-launch kernel is
+    // checked up to kNmax and no further)
+    bool fused() const { return hooked() && !no_chain && n <= kNmax && core.round_capable() && core.frames_exact(blocks(), nb); }
+    // what fft_gpu_plan_info_hip reports: 3 the one-launch path; on the fallback 2 the middle is one kernel or chained, 1 hooked passes, 0 plain
+    int path() const {
+        if (fused()) return 3;
+        if (!hooked()) return 0;
+        return (!no_chain && (core.round_capable() || core.chain_capable())) ? 2 : 1;
+    }
+
+    // h_host: n_taps complex taps; n_: the block length, 0: the plan chooses
+    bool build(RT* runtime, int n_taps_, const cpx<T>* h_host, int signal_len_, int n_signals_, int n_, int out_kind_) {
+        rt = runtime; n_taps = n_taps_; signal_len = signal_len_; n_signals = n_signals_; out_kind = out_kind_;
+        if (n_taps < 1 || !h_host || signal_len < 1 || n_signals < 1 || n_ < 0 || out_kind < FILTER_FULL || out_kind > FILTER_CENTRED) return false;
+        n = n_ ? n_ : choose_n(n_taps);
+        if (n < 1 || (n & (n - 1)) != 0 || n > (1 << 29) || n <= n_taps - 1) return false;
+        lead = n_taps - 1;
+        B = n - lead;
+        const long long ol = out_kind == FILTER_FULL ? (long long)signal_len + lead : (long long)signal_len;
+        if (ol > 0x7fffffff) return false;
+        out_len = (int)ol;
+        out_off = out_kind == FILTER_CENTRED ? lead / 2 : 0;
+        const long long per = ((long long)out_off + out_len + B - 1) / B;
+        if (per * n_signals > 0x7fffffff) return false;
+        nb = (int)per;
+        long long cb = kChunkElems / n;
+        if (cb < 1) cb = 1;
+        chunk_blocks = (int)(cb < blocks() ? cb : blocks());
+        core.prefer_chain = true;
+        core.wants_hooks = true;
+        // a block length above kNmax never takes the one-launch path and only ever runs on chunks: its (multi-pass) core and the
+        // scratch images that core owns are sized for one chunk, not for the whole execute
+        if (!core.build(rt, ilog2(n), ALGO_AUTO, n > kNmax ? chunk_blocks : (int)blocks())) return false;
+        std::vector<cpx<T>> hp((size_t)n);
+        for (auto& z : hp) { z.re = 0; z.im = 0; }
+        for (int i = 0; i < n_taps; i++) hp[(size_t)i] = h_host[i];
+        H = (cpx<T>*)rt->dmalloc((size_t)n * SZ);
+        if (!H) return false;
+        rt->h2d(H, hp.data(), (size_t)n * SZ);
+        core.execute(H, H, 1, false);  // the taps' spectrum, once
+        ok = true;
+        return true;
+    }
+
+    // out = IFFT(FFT(in) . H) for nbk contiguous blocks: the circular convolution of FusedPlan, by the same kernels
+    void middle(const cpx<T>* in, cpx<T>* out, int nbk) {
+        if (hooked() && !no_chain && core.round_capable()) {
+            ExecHooks<T> rr;
+            rr.mid_tab = H; rr.mid_mode = fftk::HOOK_MUL;
+            core.execute_round(in, out, nbk, rr);
+            return;
+        }
+        if (hooked()) {
+            ExecHooks<T> f, g;
+            f.post_tab = H; f.post_mode = fftk::HOOK_MUL;
+            if (!no_chain && core.chain_capable() && core.execute_chain(in, out, nbk, f, g)) return;
+            core.execute_hooked(in, out, nbk, false, f);
+            core.execute_hooked(out, out, nbk, true, g);
+            return;
+        }
+        const unsigned per_block = 256 * BLU_PER_THREAD;
+        const unsigned bpr = (unsigned)(((long long)n + per_block - 1) / per_block);
+        core.execute(in, out, nbk, false);
+        rt->launch(fftk::mul_store_kernel<T>, (long long)bpr * nbk, 256, (size_t)0, (const cpx<T>*)out, (long long)n, (const cpx<T>*)H, 0ll, (int)fftk::HOOK_MUL, out,
+                   (long long)n, n, (T)1, bpr);
+        core.execute(out, out, nbk, true);
+    }
+
+    // x: the signals (x_pitch elements apart; 0: signal_len); y: the outputs (y_pitch apart; 0: out_len), overlapping x nowhere -- blocks
+    // re-read their neighbours' input, so in place cannot work.  0 / -1 (bad arguments: nothing is launched)
+    int execute(const cpx<T>* x, long long x_pitch, cpx<T>* y, long long y_pitch) {
+        if (!ok || !x || !y) return -1;
+        if (x_pitch == 0) x_pitch = signal_len;
+        if (y_pitch == 0) y_pitch = out_len;
+        if (x_pitch < signal_len || y_pitch < out_len) return -1;
+        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)((long long)(n_signals - 1) * x_pitch + signal_len) * SZ;
+        const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)((long long)(n_signals - 1) * y_pitch + out_len) * SZ;
+        if (x0 < y1 && y0 < x1) return -1;
+        if (fused()) {
+            ExecHooks<T> f;
+            f.filter = true;
+            f.in_pitch = B;
+            f.frames_per_signal = nb; f.signal_pitch = x_pitch;
+            f.frame_lead = lead; f.signal_len = signal_len;
+            f.mid_tab = H; f.mid_mode = fftk::HOOK_MUL;
+            f.out_signal_pitch = y_pitch; f.out_len = out_len; f.out_off = out_off;
+            core.execute_filter(x, y, (int)blocks(), f);
+            return 0;
+        }
+        if (!work) work = (cpx<T>*)rt->dmalloc((size_t)2 * (size_t)chunk_blocks * (size_t)n * SZ);
+        if (!work) return -1;
+        cpx<T>* res = work + (size_t)chunk_blocks * (size_t)n;
+        const int log2n = ilog2(n);
+        for (long long f0 = 0; f0 < blocks(); f0 += chunk_blocks) {
+            const int cb = (int)(blocks() - f0 < chunk_blocks ? blocks() - f0 : chunk_blocks);
+            const long long total = (long long)cb * n;
+            launch_flat(rt, fftk::filter_gather_kernel<T>, total, x, x_pitch, signal_len, nb, B, lead, log2n, f0, work, total);
+            middle(work, res, cb);
+            launch_flat(rt, fftk::filter_scatter_kernel<T>, total, (const cpx<T>*)res, y, y_pitch, out_len, out_off, nb, B, lead, log2n, f0, total);
+        }
         return 0;
     }
 };

@@ -24,3 +24,8 @@
 // over the generic E = 8 kernel, +14...26 % over E = 4 radix-4; the fp64 ones lose 30 %, generic E = 8 radix-8 is fp64's best).
 // X(T, LOG2L, LOG2C)
 #define FFT_ROWS_FIXED8_LIST(X) X(float, 9, 4) X(float, 10, 3) X(float, 11, 2) X(float, 12, 1)
+// the overlap-save filter kernel (FilterPlan, fft_plans_ext.h): the hooked single-pass rows kernel, E = 4 radix-4, with HOOK = load side | store
+// side | round trip | framed load | bounded framed load | valid-part framed store (fft_kernels.h)
+#define FFT_ROWS_FILTER_HOOK (1 | 2 | 8 | 16 | 256 | 512)
+// X(T)
+#define FFT_ROWS_FILTER_LIST(X) X(float) X(double)

@@ -74,6 +74,8 @@ SIGNATURES = {
     "fft_gpu_plan_cross_frames_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_plan_cross_frames_real_hip": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_cross_chunk_hip": (_i, [_vp]),
     "fft_gpu_execute_cross_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_double]),
+    "fft_gpu_plan_filter_hip": (_vp, [_i, _vp, _i, _i, _i, _i, _i]), "fft_gpu_filter_out_len_hip": (_i, [_vp]),
+    "fft_gpu_filter_block_hip": (_i, [_vp]), "fft_gpu_execute_filter_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -102,6 +104,9 @@ SIGNATURES = {
     "fft_gpu_plan_cross_frames": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]),
     "fft_gpu_plan_cross_frames_real": (_vp, [_i, _i, _i, _i, _i, _vp, _i, _i]), "fft_gpu_cross_chunk": (_i, [_vp]),
     "fft_gpu_execute_cross_frames": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_double]),
+    # include/fft_gpu.h, behind its include of fft_hip.h
+    "fft_gpu_plan_filter": (_vp, [_i, _vp, _i, _i, _i, _i, _i]), "fft_gpu_filter_out_len": (_i, [_vp]),
+    "fft_gpu_filter_block": (_i, [_vp]), "fft_gpu_execute_filter": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -117,6 +122,8 @@ SIGNATURES = {
     "cross_correlation_fft_gpu": (_vp, [_vp, _vp, _i]),
     "fft_welch_psd_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]), "fft_welch_psd_real_gpu": (_vp, [_vp, _i, C.c_double, _i, _i]),
     "fft_coherence_real_gpu": (_vp, [_vp, _vp, _i, _i, _i]), "fft_csd_real_gpu": (_i, [_vp, _vp, _i, C.c_double, _i, _i, _vp]),
+    "fft_fir_filter_gpu": (_i, [_vp, _i, _vp, _i, _vp]),
+    "fft_design_fir_filter_gpu": (_vp, [_i, _i, C.c_double, C.c_double, C.c_double, C.c_double]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -291,6 +298,7 @@ FUSED_KINDS = {"conv": 0, "circ": 1, "autocorr": 2, "xcorr": 3, "psd": 4}
 WINDOWS = {"rect": 0, "hann": 1, "hamming": 2, "blackman": 3, "user": 4}
 FRAMES_OUT = {"stft": 0, "power": 1, "welch": 2}
 CROSS_OUT = {"csd": 0, "coherence": 1, "transfer": 2, "all": 3}
+FILTER_OUT = {"full": 0, "causal": 1, "same": 2}
 
 
 class ExtPlan:
@@ -407,6 +415,24 @@ class ExtPlan:
         if self.out == "all":
             return (self.n_signals, hb, 4), np.dtype(np.float32 if f32 else np.float64)
         return (self.n_signals, hb), np.dtype(np.complex64 if f32 else np.complex128)
+
+    @classmethod
+    def filter(cls, h, signal_len, n_signals=1, mode="full", n=0, dtype=np.complex128):
+        """Overlap-save FIR filter plan (fft_gpu_plan_filter_hip): n_signals complex signals of signal_len samples, the taps h, the
+        output of FILTER_OUT[mode] ("full": signal_len + len(h) - 1 samples, np.convolve; "causal": signal_len, lfilter(h, 1, x);
+        "same": signal_len, np.convolve 'same').  n: the block length, a power of two > len(h) - 1; 0: the plan chooses.
+        out_len, block: what the plan writes per signal and the block length it uses."""
+        dt = np.dtype(dtype)
+        taps = np.ascontiguousarray(np.asarray(h).astype(dt)).reshape(-1)
+        p = cls(init().fft_gpu_plan_filter_hip(taps.size, taps.ctypes.data if taps.size else None, signal_len, n_signals, n, FILTER_OUT[mode], _prec_of(dt)))
+        p.n_signals, p.signal_len, p.mode, p.dtype = n_signals, signal_len, mode, dt
+        p.out_len = p.lib.fft_gpu_filter_out_len_hip(p.handle)
+        p.block = p.lib.fft_gpu_filter_block_hip(p.handle)
+        return p
+
+    def execute_filter(self, d_x, d_y, x_pitch=0, y_pitch=0):
+        if self.lib.fft_gpu_execute_filter_hip(self.handle, d_x, x_pitch, d_y, y_pitch) != 0:
+            raise RuntimeError("fft_gpu_execute_filter_hip failed")
 
     def execute_cross(self, d_x, d_y, d_out, x_pitch=0, y_pitch=0, sample_rate=1.0):
         if self.lib.fft_gpu_execute_cross_frames_hip(self.handle, d_x, x_pitch, d_y, y_pitch, d_out, sample_rate) != 0:
@@ -544,6 +570,60 @@ def _frames(x, n, hop, window, out, fs):
     o.free()
     plan.destroy()
     return res[0] if x.ndim == 1 else res
+
+
+def fir_filter(x, h, mode="full", n=0, plan=None):
+    """x: [signals, len] (or [len]) complex64 / complex128, h: the FIR taps -> [signals, out_len]: every signal convolved with h by
+    overlap-save on the device (ExtPlan.filter).  mode "full": np.convolve(x, h); "causal": its first len samples, y[t] = sum_j h[j]
+    x[t - j]; "same": np.convolve(x, h, 'same').  n: the block length (0: the plan's choice).  plan: an ExtPlan.filter to reuse (h,
+    mode and n are then the plan's).  Convenience: a float32 / float64 x with real h is widened to complex and the real part of the
+    result is returned -- no packed real path exists."""
+    x = np.asarray(x)
+    real = x.dtype in (np.dtype(np.float32), np.dtype(np.float64))
+    if real and np.iscomplexobj(h):
+        raise ValueError("a real signal takes real taps")
+    if real:
+        x = x.astype(np.complex64 if x.dtype == np.float32 else np.complex128)
+    if x.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+        raise ValueError("fir_filter takes float32, float64, complex64 or complex128 signals")
+    x = np.ascontiguousarray(x)
+    x2 = x.reshape(1, -1) if x.ndim == 1 else x
+    own = plan is None
+    if own:
+        plan = ExtPlan.filter(h, x2.shape[1], x2.shape[0], mode, n, x2.dtype)
+    elif (plan.n_signals, plan.signal_len, plan.dtype) != (x2.shape[0], x2.shape[1], x2.dtype):
+        raise ValueError("the plan was made for another shape or precision")
+    shape = (x2.shape[0], plan.out_len)
+    a, o = DeviceBuffer(x2.nbytes), DeviceBuffer(shape[0] * shape[1] * x2.dtype.itemsize)
+    try:
+        a.upload(x2)
+        plan.execute_filter(a.ptr, o.ptr, 0, 0)
+        if plan.sync() != 0:
+            raise RuntimeError("execute failed")
+        res = o.download(shape, x2.dtype)
+    finally:
+        a.free()
+        o.free()
+        if own:
+            plan.destroy()
+    if real:
+        res = np.ascontiguousarray(res.real)
+    return res[0] if x.ndim == 1 else res
+
+
+FIR_TYPES = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3, "custom": 4}
+
+
+def design_fir(taps, kind, cutoff_low=0.0, cutoff_high=0.0, fs=1.0, transition=0.0):
+    """FIR taps by frequency sampling (fft_design_fir_filter_gpu: the reference's design_fir_filter, inverse transform on the
+    device): kind a name of FIR_TYPES or its number, cutoffs, sample rate and transition width in Hz -> [taps] complex128."""
+    lib = init()
+    ptr = lib.fft_design_fir_filter_gpu(taps, FIR_TYPES[kind] if isinstance(kind, str) else int(kind), cutoff_low, cutoff_high, fs, transition)
+    if not ptr:
+        raise RuntimeError("fft_design_fir_filter_gpu failed")
+    h = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_double)), shape=(taps, 2)).copy().view(np.complex128).reshape(taps)
+    lib.fft_free(ptr)
+    return h
 
 
 def stft(x, n, hop, window="hann"):

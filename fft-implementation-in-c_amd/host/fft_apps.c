@@ -1,7 +1,9 @@
 /*
  * fft_apps.c -- host-array front ends of the fused consumers (include/fft_apps.h): the reference's
- * applications/convolution.c:34-96 and applications/power_spectrum.c:58-86, 133-190 as one fused device plan each.
+ * applications/convolution.c:34-96 and applications/power_spectrum.c:58-86, 133-190 as one fused device plan each, and
+ * applications/fft_filtering.c's FIR design with FIR filtering of a long signal as one overlap-save filter plan.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -197,4 +199,77 @@ double* fft_coherence_real_gpu(const double* x, const double* y, int n, int wind
 int fft_csd_real_gpu(const double* x, const double* y, int n, double sample_rate, int window_size, int overlap, complex_t* pxy) {
     if (window_size < 4) return -1;
     return run_cross(1, x, y, n, sample_rate, window_size, overlap, FFT_GPU_CROSS_CSD, pxy, ((size_t)window_size / 2 + 1) * sizeof(complex_t));
+}
+
+/* y = x * h through ONE overlap-save filter plan (fft_gpu_plan_filter_hip, FULL output): any nx, the block length is the plan's */
+int fft_fir_filter_gpu(const complex_t* x, int nx, const complex_t* h, int nh, complex_t* y) {
+    if (!x || !h || !y || nx <= 0 || nh <= 0 || ensure_gpu() != 0) return -1;
+    const size_t ny = (size_t)nx + (size_t)nh - 1;
+    int rc = -1;
+    fft_gpu_plan_t plan = fft_gpu_plan_filter_hip(nh, h, nx, 1, 0, FFT_GPU_FILTER_FULL, FFT_PREC_F64);
+    fft_gpu_memory_t dx = plan ? fft_gpu_alloc((size_t)nx) : NULL;
+    fft_gpu_memory_t dy = plan ? fft_gpu_alloc(ny) : NULL;
+    if (plan && dx && dy) {
+        if (fft_gpu_copy_h2d_bytes_hip(dx, x, (size_t)nx * sizeof(complex_t)) == 0 &&
+            fft_gpu_execute_filter_hip(plan, fft_gpu_memory_ptr(dx), 0, fft_gpu_memory_ptr(dy), 0) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+            fft_gpu_copy_d2h_bytes_hip(y, dy, ny * sizeof(complex_t)) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(dx);
+    fft_gpu_free(dy);
+    fft_gpu_destroy_plan(plan);
+    return rc;
+}
+
+/* magnitude of the sampled response at frequency f (Hz, signed): the ideal response of the filter type, then -- low-pass and high-pass
+ * only, as in the reference -- the raised-cosine transition of width tw centred on the cutoff */
+static double fir_response(int type, double f, double lo, double hi, double tw) {
+    const double a = fabs(f);
+    double mag;
+    switch (type) {
+        case 0: mag = a <= lo ? 1.0 : 0.0; break;
+        case 1: mag = a >= hi ? 1.0 : 0.0; break;
+        case 2: mag = (a >= lo && a <= hi) ? 1.0 : 0.0; break;
+        case 3: mag = (a < lo || a > hi) ? 1.0 : 0.0; break;
+        default: mag = 1.0; break;
+    }
+    if (type == 0 && a > lo - tw / 2 && a < lo + tw / 2) mag = 0.5 * (1.0 + cos(PI * ((a - (lo - tw / 2)) / tw)));
+    if (type == 1 && a > hi - tw / 2 && a < hi + tw / 2) mag = 0.5 * (1.0 - cos(PI * ((a - (hi - tw / 2)) / tw)));
+    return mag;
+}
+
+complex_t* fft_design_fir_filter_gpu(int taps, int type, double cutoff_low, double cutoff_high, double sample_rate, double transition_width) {
+    if (taps < 2 || taps > (1 << 26) || type < 0 || type > 4 || !(sample_rate > 0.0)) {
+        fprintf(stderr, "Error: FIR design needs 2 <= taps <= 2^26, a filter type 0 ... 4 and a positive sample rate\n");
+        return NULL;
+    }
+    if (ensure_gpu() != 0) return NULL;
+    const int n = next_power_of_two(taps * 4);
+    complex_t* H = allocate_complex_array(n);
+    complex_t* h = allocate_complex_array(taps);
+    int rc = -1;
+    if (H && h) {
+        const double bin = sample_rate / n;
+        for (int k = 0; k < n; k++) H[k] = fir_response(type, (k > n / 2 ? k - n : k) * bin, cutoff_low, cutoff_high, transition_width);
+        fft_gpu_plan_t plan = fft_gpu_plan_1d(n, 1, FFT_INVERSE);
+        fft_gpu_memory_t d = plan ? fft_gpu_alloc((size_t)n) : NULL;
+        if (plan && d) {
+            if (fft_gpu_copy_h2d_bytes_hip(d, H, (size_t)n * sizeof(complex_t)) == 0 &&
+                fft_gpu_execute_ptr(plan, fft_gpu_memory_ptr(d), fft_gpu_memory_ptr(d)) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+                fft_gpu_copy_d2h_bytes_hip(H, d, (size_t)n * sizeof(complex_t)) == 0)
+                rc = 0;
+        }
+        fft_gpu_free(d);
+        fft_gpu_destroy_plan(plan);
+    }
+    if (rc == 0) {
+        const int shift = taps / 2;
+        for (int i = 0; i < taps; i++) h[i] = H[(i - shift + n) % n] * (0.54 - 0.46 * cos(TWO_PI * i / (taps - 1)));
+    }
+    if (H) free_complex_array(H);
+    if (rc != 0) {
+        if (h) free_complex_array(h);
+        return NULL;
+    }
+    return h;
 }

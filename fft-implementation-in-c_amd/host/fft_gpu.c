@@ -243,6 +243,22 @@ int fft_gpu_execute_cross_frames(fft_gpu_plan_t plan, const void* d_x, long long
     return fft_gpu_execute_cross_frames_hip(plan, d_x, x_pitch, d_y, y_pitch, d_out, sample_rate);
 }
 
+/* filter plans: overlap-save FIR filtering of long signals */
+fft_gpu_plan_t fft_gpu_plan_filter(int n_taps, const void* h_host, int signal_len, int n_signals, int n, fft_gpu_filter_out_t out,
+                                   fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_filter")) return NULL;
+    return fft_gpu_plan_filter_hip(n_taps, h_host, signal_len, n_signals, n, out, prec);
+}
+
+int fft_gpu_filter_out_len(fft_gpu_plan_t plan) { return fft_gpu_filter_out_len_hip(plan); }
+
+int fft_gpu_filter_block(fft_gpu_plan_t plan) { return fft_gpu_filter_block_hip(plan); }
+
+int fft_gpu_execute_filter(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
+    if (!backend_is_hip("fft_gpu_execute_filter")) return -1;
+    return fft_gpu_execute_filter_hip(plan, d_x, x_pitch, d_y, y_pitch);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

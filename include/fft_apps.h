@@ -7,6 +7,7 @@
  *   compute_periodogram, autocorrelation_fft,
  *   cross_correlation_fft                      applications/power_spectrum.c:58-86, 133-190
  *   welch_psd (here fft_welch_psd_gpu)         applications/power_spectrum.c:87-130
+ *   design_fir_filter (fft_design_fir_filter_gpu) applications/fft_filtering.c:135-161
  * with a `_gpu` suffix, host arrays in and out, and int 0 / -1 (or NULL) instead of exit().  Each is ONE fused plan on the
  * device (fft_hip.h: fft_gpu_plan_fused_hip): forward transform, element-wise step and inverse transform, with the zero
  * padding, the spectral product and the truncation riding on the FFT passes.  Batched, device-resident use goes through
@@ -50,6 +51,15 @@ double* fft_coherence_real_gpu(const double* x, const double* y, int n, int wind
 /* Cross-spectral density Pxy = c_k mean_w conj(X_w) Y_w of two real signals (scipy's csd convention): pxy has room for
  * window_size/2 + 1 values.  0 / -1. */
 int fft_csd_real_gpu(const double* x, const double* y, int n, double sample_rate, int window_size, int overlap, complex_t* pxy);
+/* FIR filtering of a long signal: y[0 .. nx + nh - 2] = x * h, the results of fft_convolution_gpu, through ONE overlap-save filter
+ * plan (fft_gpu_plan_filter_hip: blocks of a few thousand samples, one kernel launch) for any nx.  0 / -1. */
+int fft_fir_filter_gpu(const complex_t* x, int nx, const complex_t* h, int nh, complex_t* y);
+/* FIR design by frequency sampling (design_fir_filter, applications/fft_filtering.c:135-161, its params struct flattened): the
+ * response of `type` (the reference's filter_type_t: 0 low-pass, 1 high-pass, 2 band-pass, 3 band-stop, 4 all-pass) sampled at
+ * next_power_of_two(4 taps) points, with a raised-cosine transition of transition_width Hz for low-pass and high-pass only, its
+ * inverse transform (on the device) shifted by taps / 2 and Hamming-windowed with the taps - 1 denominator.  taps >= 2.  A malloc'd
+ * (allocate_complex_array) array of taps values freed by the caller; NULL on failure and without a device. */
+complex_t* fft_design_fir_filter_gpu(int taps, int type, double cutoff_low, double cutoff_high, double sample_rate, double transition_width);
 
 #ifdef __cplusplus
 }

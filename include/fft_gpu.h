@@ -71,4 +71,17 @@ int fft_gpu_set_device(int device);        /* 0 / -1; real here (a stub in the r
 
 #include "fft_hip.h"
 
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* filter plans (fft_gpu_plan_filter_hip, fft_hip.h) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_filter(int n_taps, const void* h_host, int signal_len, int n_signals, int n, fft_gpu_filter_out_t out,
+                                   fft_precision_t prec);
+int fft_gpu_filter_out_len(fft_gpu_plan_t plan);
+int fft_gpu_filter_block(fft_gpu_plan_t plan);
+int fft_gpu_execute_filter(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch);
+#ifdef __cplusplus
+}
+#endif
+
 #endif /* FFT_GPU_H */

@@ -279,6 +279,30 @@ int fft_gpu_cross_chunk_hip(fft_gpu_plan_t plan);    /* C, frames per chunk of t
  * pointers, short pitches and an overlapping output return -1; nothing is launched then. */
 int fft_gpu_execute_cross_frames_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch,
                                      void* d_out, double sample_rate);
+/* Overlap-save FIR filtering of n_signals long signals of signal_len complex samples with n_taps fixed complex taps (what the
+ * reference's applications/fft_filtering.c is for, as a device plan).  The signals are cut into overlapping blocks of n samples (a
+ * power of two > n_taps - 1; 0: the plan chooses min(nmax, max(256, next_pow2(4 n_taps))), nmax = 4096 fp32 / 2048 fp64, and
+ * next_pow2(4 n_taps) for taps too long for that -- an unmeasured guess) that advance by B = n - (n_taps - 1); every block is
+ * transformed, multiplied by FFT_n(taps) (computed once at plan time), transformed back, and its last B values go straight into
+ * the output signal.  Where n fits one hooked pass (n <= nmax) that is ONE kernel launch and one round trip of the data: no
+ * [blocks][n] copy in or out; fft_gpu_plan_info_hip then reports fused = 3.  Any other n, and FFT_GPU_OPT_NO_FUSION /
+ * FFT_GPU_OPT_NO_CHAIN, take a gather kernel, the fused-convolution middle and a scatter kernel on bounded chunks of blocks
+ * (fused = 2 / 1 / 0 by what the middle runs).  info: n = the block length, batch = n_signals * blocks per signal.
+ * NULL: n_taps < 1, signal_len < 1, n_signals < 1, n not a power of two, n <= n_taps - 1, more than 2^31 - 1 blocks or output
+ * samples, a failed allocation. */
+typedef enum { FFT_GPU_FILTER_FULL = 0,     /* out_len = signal_len + n_taps - 1, np.convolve 'full'                    */
+               FFT_GPU_FILTER_CAUSAL = 1,   /* out_len = signal_len, y[t] = sum_j h[j] x[t-j] (scipy lfilter(h, 1, x))  */
+               FFT_GPU_FILTER_CENTRED = 2 } /* out_len = signal_len, full[(n_taps-1)/2 ...], np.convolve 'same'         */ fft_gpu_filter_out_t;
+fft_gpu_plan_t fft_gpu_plan_filter_hip(int n_taps, const void* h_host /* n_taps complex of prec */, int signal_len, int n_signals,
+                                       int n /* block length, power of two > n_taps - 1; 0: the plan chooses */,
+                                       fft_gpu_filter_out_t out, fft_precision_t prec);
+int fft_gpu_filter_out_len_hip(fft_gpu_plan_t plan);   /* -1: not a filter plan */
+int fft_gpu_filter_block_hip(fft_gpu_plan_t plan);     /* n actually used; -1: not a filter plan */
+/* async on the plan's stream.  Signal s is read at d_x + s * x_pitch and written at d_y + s * y_pitch (elements; 0: signal_len /
+ * out_len); the elements between signals are neither read nor written.  -1, nothing launched: NULL pointers, a pitch smaller than
+ * its row, d_y overlapping d_x (blocks re-read their neighbours' input: in place cannot work). */
+int fft_gpu_execute_filter_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch /* 0: signal_len */,
+                               void* d_y, long long y_pitch /* 0: out_len */);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
