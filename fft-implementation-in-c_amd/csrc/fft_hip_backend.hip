@@ -311,7 +311,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter, 9 2D convolution
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -327,9 +327,11 @@ struct fft_gpu_plan {
     ffteng::CrossFramesPlan<double, HipRT>* x64 = nullptr;
     ffteng::FilterPlan<float, HipRT>* s32 = nullptr;  // overlap-save FIR filtering of long signals
     ffteng::FilterPlan<double, HipRT>* s64 = nullptr;
+    ffteng::Conv2DPlan<float, HipRT>* c32 = nullptr;  // 2D convolution / spectrum filtering of images
+    ffteng::Conv2DPlan<double, HipRT>* c64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9 };
 
 namespace {
 
@@ -439,6 +441,13 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
     if (p->x64) f(&p->x64->inner.core);
     if (p->s32) f(&p->s32->core);
     if (p->s64) f(&p->s64->core);
+    auto conv = [&](auto* c) {
+        if (!c) return;
+        f(&c->rowp);
+        if (c->round.colp.ok) f(&c->round.colp);
+        two(c->fwd); two(c->inv);
+    };
+    conv(p->c32); conv(p->c64);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -495,6 +504,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->i32 || p->i64) return -1;  // inverse frames plans take a signal pitch: fft_gpu_execute_iframes_hip
     else if (p->x32 || p->x64) return -1;  // cross frames plans take two signals: fft_gpu_execute_cross_frames_hip
     else if (p->s32 || p->s64) return -1;  // filter plans take two pitches: fft_gpu_execute_filter_hip
+    else if (p->c32 || p->c64) return -1;  // 2D convolution plans take two pitches: fft_gpu_execute_conv2d_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -763,6 +773,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->x64;
         delete p->s32;
         delete p->s64;
+        delete p->c32;
+        delete p->c64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -1120,6 +1132,57 @@ int fft_gpu_execute_filter_hip(fft_gpu_plan_t p, const void* d_x, long long x_pi
     return 0;
 }
 
+// 2D convolution / spectrum filtering of row-major images (fft_plans_ext.h Conv2DPlan); k_host: krows x kcols complex of `prec` in host
+// memory (SPECTRUM: the rows x cols spectrum itself)
+fft_gpu_plan_t fft_gpu_plan_conv2d_hip(int rows, int cols, int krows, int kcols, const void* k_host, int n_matrices, fft_gpu_conv2d_t mode,
+                                       fft_precision_t prec) {
+    int P = 0, Q = 0, orows = 0, ocols = 0;
+    if (!k_host || n_matrices < 1 || !ffteng::Conv2DPlan<float, HipRT>::sizes(rows, cols, krows, kcols, (int)mode, P, Q, orows, ocols)) {
+        fprintf(stderr, "fft_hip: invalid 2D convolution plan arguments (image %dx%d kernel %dx%d matrices=%d mode=%d)\n", rows, cols, krows, kcols, n_matrices,
+                (int)mode);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(Q, n_matrices, -1, prec, PLAN_CONV2D);
+    if (!p) return NULL;
+    p->rows = rows; p->cols = cols;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->c32 = new (std::nothrow) ffteng::Conv2DPlan<float, HipRT>();
+        ok = p->c32 && p->c32->build(&p->rt, rows, cols, krows, kcols, (const fftk::cpx<float>*)k_host, n_matrices, (int)mode);
+    } else {
+        p->c64 = new (std::nothrow) ffteng::Conv2DPlan<double, HipRT>();
+        ok = p->c64 && p->c64->build(&p->rt, rows, cols, krows, kcols, (const fftk::cpx<double>*)k_host, n_matrices, (int)mode);
+    }
+    return finish_plan(p, ok, "2D convolution");
+}
+#define FFT_CONV2D_GETTER(name, field)      \
+    int name(fft_gpu_plan_t p) {            \
+        if (!p) return -1;                  \
+        if (p->c32) return p->c32->field;   \
+        if (p->c64) return p->c64->field;   \
+        return -1;                          \
+    }
+FFT_CONV2D_GETTER(fft_gpu_conv2d_out_rows_hip, out_rows)
+FFT_CONV2D_GETTER(fft_gpu_conv2d_out_cols_hip, out_cols)
+FFT_CONV2D_GETTER(fft_gpu_conv2d_padded_rows_hip, P)
+FFT_CONV2D_GETTER(fft_gpu_conv2d_padded_cols_hip, Q)
+#undef FFT_CONV2D_GETTER
+// async on the plan's stream.  d_x: the images, x_pitch elements apart (0: rows * cols); d_y: the outputs, y_pitch apart (0: out_rows *
+// out_cols); the two must not overlap
+int fft_gpu_execute_conv2d_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
+    if (!p || !d_x || !d_y || (!p->c32 && !p->c64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->c32 ? p->c32->execute((const fftk::cpx<float>*)d_x, x_pitch, (fftk::cpx<float>*)d_y, y_pitch)
+                          : p->c64->execute((const fftk::cpx<double>*)d_x, x_pitch, (fftk::cpx<double>*)d_y, y_pitch);
+    if (rc != 0) return -1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
 int fft_gpu_plan_set_stream_hip(fft_gpu_plan_t p, void* hip_stream) {
     if (!p) return -1;
     (void)hipStreamSynchronize(p->rt.stream);
@@ -1366,7 +1429,9 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->x64) p->x64->inner.no_fusion = value != 0;
             if (p->s32) p->s32->no_fusion = value != 0;
             if (p->s64) p->s64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64) ? 0 : -1;
+            if (p->c32) p->c32->no_fusion = value != 0;
+            if (p->c64) p->c64->no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64 || p->c32 || p->c64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
@@ -1537,6 +1602,23 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->s32) fill_filter(p->s32);
     if (p->s64) fill_filter(p->s64);
+    // 2D convolution: n = Q, batch = matrices, factors = {Q, P, Q}; n_passes = HBM round trips of the work image (3 the column round, 5 the
+    // padded fallback); fused: 1 the column round kernel runs
+    auto fill_conv2d = [&](auto* c) {
+        fill(&c->rowp);
+        info->n = c->Q;
+        info->batch = c->n_matrices;
+        info->n_passes = c->passes();
+        info->factors[0] = c->Q; info->factors[1] = c->P; info->factors[2] = c->Q; info->factors[3] = 0;
+        info->fused = c->fused() ? 1 : 0;
+        const size_t esz = sizeof(*c->H), q = (size_t)c->Q, m = (size_t)c->n_matrices;
+        info->workspace_bytes += (size_t)c->P * q * esz;
+        if (c->work1) info->workspace_bytes += m * (size_t)c->rows * q * esz;
+        if (c->work2) info->workspace_bytes += m * (size_t)c->out_rows * q * esz;
+        if (c->fwork) info->workspace_bytes += m * (size_t)c->P * q * esz;
+    };
+    if (p->c32) fill_conv2d(p->c32);
+    if (p->c64) fill_conv2d(p->c64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

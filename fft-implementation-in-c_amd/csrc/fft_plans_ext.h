@@ -1,12 +1,13 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
-// overlapping frames, the inverse STFT by overlap-add, and overlap-save FIR filtering).  Templated on the same runtime policy RT as the engine, so the
+// overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, and 2D convolution / spectrum filtering).  Templated on the same runtime policy RT as the engine, so the
 // unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
 #include "fft_engine.h"
 #include "fft_kernels_ext.h"
+#include "fft_kernels_conv2d.h"
 
 namespace ffteng {
 
@@ -838,6 +839,251 @@ class FilterPlan {
             middle(work, res, cb);
             launch_flat(rt, fftk::filter_scatter_kernel<T>, total, (const cpx<T>*)res, y, y_pitch, out_len, out_off, nb, B, lead, log2n, f0, total);
         }
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// 2D convolution and frequency-domain image filtering: y = IFFT2( FFT2(x zero padded to P x Q) . H ) for n_matrices row-major
+// rows x cols images and ONE kernel fixed at plan time (reference applications/convolution.c:99-109, fft_convolution_2d, is a
+// placeholder; applications/image_fft.c:147-235 masks the 2D spectrum of an image).
+//   FULL      out (rows + krows - 1) x (cols + kcols - 1)                      scipy.signal.convolve2d 'full'
+//   SAME      out rows x cols           = full[(krows-1)/2 ..][(kcols-1)/2 ..]
+//   VALID     out (rows - krows + 1) x (cols - kcols + 1), krows <= rows, kcols <= cols    = full[krows-1 ..][kcols-1 ..]
+//   CIRCULAR  rows, cols powers of two, krows <= rows, kcols <= cols: the kernel wraps, out rows x cols
+//   SPECTRUM  rows, cols powers of two, k_host IS H[rows][cols] in natural (unshifted) order: out = IFFT2(FFT2(x) . H)
+// P = next_pow2(rows + krows - 1), Q = next_pow2(cols + kcols - 1) for the three linear modes, P = rows, Q = cols otherwise.  The
+// result carries ONE 1 / (P Q), like Plan2D (the reference's fft_2d divides twice, image_fft.c:64-71).
+//
+// The shift.  At plan time the kernel goes into a [P][Q] host array at k'[(i - sr) mod P][(j - sc) mod Q] = k[i][j], with the
+// output offset (sr, sc) = ((krows-1)/2, (kcols-1)/2) for SAME, (krows-1, kcols-1) for VALID, (0, 0) otherwise; H = FFT2(k') is
+// computed once on the device by a Plan2D.  The circular convolution c of the padded image with k' is then
+//   c[u][v] = sum over (s, t) with s = u + sr (mod P), t = v + sc (mod Q) of full[s][t],
+// full being the linear convolution, supported on 0 <= s <= F - 1 = rows + krows - 2 (and the same along the columns).  Every wanted
+// output has 0 <= u < out_rows, and in each mode u + sr lies in [0, F - 1]: FULL [0, F - 1]; SAME [sr, rows - 1 + sr] with
+// sr <= krows - 1; VALID [krows - 1, rows - 1].  The other members of its residue class are u + sr + P >= P >= F (beyond the support)
+// and u + sr - P <= F - 1 - P < 0 (before it): exactly one term, c[u][v] = full[u + sr][v + sc].  So no wanted output aliases, the
+// wanted block starts at [0][0], and no pass needs an offset.
+//
+// Fused path (three HBM round trips of compact work images, nothing zero-filled, copied or cropped):
+//   1  rows forward   rows * M transforms of length Q, execute_hooked with n_in = cols: the padding COLUMNS are never read, the
+//                     padding ROWS are never transformed or stored -> work1 [M][rows][Q]
+//   2  column round   tile_fft_colround_kernel: forward column stages, product with H, inverse column stages on one P x C tile;
+//                     loads rows < rows, stores rows < out_rows -> work2 [M][out_rows][Q]
+//   3  rows inverse   out_rows * M transforms with n_out = out_cols, straight into the caller's matrices
+// taken where the one-pass column plan (Pow2Plan::build_columns) exists with E = 8 (P >= 8) and row segments of at least
+// min_seg_bytes = 64 bytes -- Plan2D's own criterion for its one-pass column -- and the row plan is hook capable.  A caller's base
+// pointer that is not 16-byte aligned (or, with a matrix pitch of its own, a pitch that is no multiple of 16 bytes) keeps steps 2 and
+// the other end but pads / crops that end's rows with pad_mul_kernel / mul_store_kernel around the plain row plan.
+// Fallback (everything else and no_fusion; five round trips of the padded image, correct, not tuned): conv2d_pad_kernel into
+// [M][P][Q], forward Plan2D, mul_store_kernel against H, inverse Plan2D, conv2d_crop_kernel.  Its plans and image are made at the
+// first execute that needs them.
+// ---------------------------------------------------------------------------
+enum Conv2DMode { CONV2D_FULL = 0, CONV2D_SAME = 1, CONV2D_VALID = 2, CONV2D_CIRCULAR = 3, CONV2D_SPECTRUM = 4 };
+
+// the column round as a step of its own: P x Q matrices (Q any multiple of the 16-byte lane access), rows_in rows in, rows_out rows out
+template <typename T, typename RT>
+class ColRoundStep {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    RT* rt = nullptr;
+    Pow2Plan<T, RT> colp;  // build_columns: the tile and the stage tables
+    int log2P = 0, Q = 0;
+    bool ok = false;
+    bool build(RT* runtime, int log2P_, int Q_, int n_matrices, int min_seg_bytes) {
+        rt = runtime; log2P = log2P_; Q = Q_;
+        if (!colp.build_columns(rt, log2P, Q, n_matrices)) return false;
+        const PassDesc& a = colp.passes[0];
+        ok = a.E == 8 && a.log2H == 0 && a.nthreads <= 512 && a.seg_bytes >= min_seg_bytes;
+        return ok;
+    }
+    int tile_cols() const { return ok ? 1 << colp.passes[0].log2C : 0; }
+    // out[m][K][c] = (1/P) IFFT_P( FFT_P(in[m][.][c], rows >= rows_in zero) . H[.][c] )[K], K < rows_out
+    void run(const cpx<T>* in, int rows_in, const cpx<T>* H, cpx<T>* out, int rows_out, int nm) {
+        const PassDesc& a = colp.passes[0];
+        fftk::ColRoundParams<T> q;
+        memset(&q, 0, sizeof(q));
+        q.in = in; q.out = out; q.spec = H; q.tables = colp.pass_tables[0];
+        q.group_bytes = a.group_bytes; q.tables_bytes = a.tables_elems * SZ; q.off_tables = a.off_tables; q.o_sb = a.o_sb; q.sa_bits = a.sa_bits;
+        q.log2L = a.log2L; q.log2C = a.log2C; q.n_ct = a.n_ct; q.n_cols = Q;
+        q.rows_in = rows_in; q.rows_out = rows_out;
+        q.in_b = (long long)rows_in * Q; q.out_b = (long long)rows_out * Q; q.ld = Q;
+        q.n_tiles = (long long)nm * a.n_ct;
+        q.nt = a.seg_bytes >= 128 ? 3 : 0;  // the tile passes' rule (Pow2Plan::pass_params): whole 128-byte lines only; not measured here
+        q.scale = (T)(1.0L / (long double)(1ll << log2P));
+        int per_cu = rt->max_blocks_per_cu(fftk::tile_fft_colround_kernel<T>, a.nthreads, (size_t)a.smem_bytes);
+        if (per_cu < 1) per_cu = 1;
+        long long grid = (long long)rt->num_cus() * per_cu;
+        if (grid > q.n_tiles) grid = q.n_tiles;
+        rt->launch(fftk::tile_fft_colround_kernel<T>, grid, a.nthreads, (size_t)a.smem_bytes, q);
+    }
+};
+
+template <typename T, typename RT>
+class Conv2DPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    RT* rt = nullptr;
+    int rows = 0, cols = 0, krows = 0, kcols = 0, n_matrices = 0, mode = 0;
+    int P = 0, Q = 0, out_rows = 0, out_cols = 0;
+    Pow2Plan<T, RT> rowp;          // length Q, hooked ends
+    ColRoundStep<T, RT> round;
+    cpx<T>* H = nullptr;           // [P][Q]: FFT2 of the placed kernel, or the caller's spectrum
+    cpx<T>* work1 = nullptr;       // fused: [M][rows][Q]
+    cpx<T>* work2 = nullptr;       // fused: [M][out_rows][Q]
+    Plan2D<T, RT>* fwd = nullptr;  // fallback (made at its first use)
+    Plan2D<T, RT>* inv = nullptr;
+    cpx<T>* fwork = nullptr;       // fallback: [M][P][Q]
+    int min_seg_bytes = 64;        // the fused path's row-segment criterion (tests narrow it to reach narrow tiles)
+    bool ok = false;
+    bool no_fusion = false;
+    ~Conv2DPlan() {
+        delete fwd;
+        delete inv;
+        if (!rt) return;
+        rt->dfree(H); rt->dfree(work1); rt->dfree(work2); rt->dfree(fwork);
+    }
+    bool fusable() const { return ok && round.ok && rowp.ok && rowp.hook_capable() && work1 && work2; }
+    bool fused() const { return fusable() && !no_fusion; }
+    int passes() const { return fused() ? 3 : 5; }  // HBM round trips of the work image
+
+    static bool sizes(int rows, int cols, int krows, int kcols, int mode, int& P, int& Q, int& orows, int& ocols) {
+        if (rows < 1 || cols < 1 || krows < 1 || kcols < 1 || mode < CONV2D_FULL || mode > CONV2D_SPECTRUM) return false;
+        const long long fr = (long long)rows + krows - 1, fc = (long long)cols + kcols - 1;
+        if (mode >= CONV2D_CIRCULAR) {
+            if ((rows & (rows - 1)) != 0 || (cols & (cols - 1)) != 0) return false;
+            if (mode == CONV2D_CIRCULAR ? (krows > rows || kcols > cols) : (krows != rows || kcols != cols)) return false;
+            P = rows; Q = cols; orows = rows; ocols = cols;
+        } else {
+            if (mode == CONV2D_VALID && (krows > rows || kcols > cols)) return false;
+            if (fr > (1ll << 30) || fc > (1ll << 30)) return false;
+            long long p = 1, q = 1;
+            while (p < fr) p <<= 1;
+            while (q < fc) q <<= 1;
+            P = (int)p; Q = (int)q;
+            orows = mode == CONV2D_FULL ? (int)fr : mode == CONV2D_SAME ? rows : rows - krows + 1;
+            ocols = mode == CONV2D_FULL ? (int)fc : mode == CONV2D_SAME ? cols : cols - kcols + 1;
+        }
+        return (long long)P * Q <= (1ll << 30);
+    }
+
+    // k_host: krows x kcols complex values, row-major (SPECTRUM: H itself)
+    bool build(RT* runtime, int rows_, int cols_, int krows_, int kcols_, const cpx<T>* k_host, int n_matrices_, int mode_, int min_seg = 64) {
+        rt = runtime; rows = rows_; cols = cols_; krows = krows_; kcols = kcols_; n_matrices = n_matrices_; mode = mode_; min_seg_bytes = min_seg;
+        if (!k_host || n_matrices < 1 || !sizes(rows, cols, krows, kcols, mode, P, Q, out_rows, out_cols)) return false;
+        if ((long long)P * n_matrices > 0x7fffffff || (long long)Q * n_matrices > 0x7fffffff) return false;
+        const size_t pq = (size_t)P * (size_t)Q;
+        {   // H
+            std::vector<cpx<T>> hp(pq);
+            if (mode == CONV2D_SPECTRUM) {
+                std::copy(k_host, k_host + pq, hp.begin());
+            } else {
+                for (auto& z : hp) { z.re = 0; z.im = 0; }
+                const int sr = mode == CONV2D_SAME ? (krows - 1) / 2 : mode == CONV2D_VALID ? krows - 1 : 0;
+                const int sc = mode == CONV2D_SAME ? (kcols - 1) / 2 : mode == CONV2D_VALID ? kcols - 1 : 0;
+                for (int i = 0; i < krows; i++)
+                    for (int j = 0; j < kcols; j++)
+                        hp[(size_t)((i - sr + P) % P) * Q + (size_t)((j - sc + Q) % Q)] = k_host[(size_t)i * kcols + j];
+            }
+            H = (cpx<T>*)rt->dmalloc(pq * SZ);
+            if (!H) return false;
+            rt->h2d(H, hp.data(), pq * SZ);
+            if (mode != CONV2D_SPECTRUM) {
+                Plan2D<T, RT> once;
+                if (!once.build(rt, P, Q, -1, 1)) return false;
+                once.execute(H, H, 1);  // the kernel's spectrum, once
+            }
+        }
+        ok = true;
+        const int big = rows > out_rows ? rows : out_rows;
+        if (P >= 8 && Q >= V && round.build(rt, ilog2(P), Q, n_matrices, min_seg_bytes)) {
+            rowp.wants_hooks = true;
+            if (rowp.build(rt, ilog2(Q), ALGO_AUTO, big * n_matrices) && rowp.hook_capable()) {
+                work1 = (cpx<T>*)rt->dmalloc((size_t)n_matrices * (size_t)rows * (size_t)Q * SZ);
+                work2 = (cpx<T>*)rt->dmalloc((size_t)n_matrices * (size_t)out_rows * (size_t)Q * SZ);
+                if (!work1 || !work2) { ok = false; return false; }
+            }
+        }
+        if (!fusable() && !ensure_fallback()) { ok = false; return false; }
+        return true;
+    }
+
+    bool ensure_fallback() {
+        if (fwd && inv && fwork) return true;
+        if (!fwd) {
+            fwd = new Plan2D<T, RT>();
+            if (!fwd->build(rt, P, Q, -1, n_matrices)) { delete fwd; fwd = nullptr; return false; }
+        }
+        if (!inv) {
+            inv = new Plan2D<T, RT>();
+            if (!inv->build(rt, P, Q, 1, n_matrices)) { delete inv; inv = nullptr; return false; }
+        }
+        if (!fwork) fwork = (cpx<T>*)rt->dmalloc((size_t)n_matrices * (size_t)P * (size_t)Q * SZ);
+        return fwork != nullptr;
+    }
+
+    // x: the images (x_pitch elements apart; 0: rows * cols); y: the outputs (y_pitch apart; 0: out_rows * out_cols), overlapping x
+    // nowhere.  0 / -1 (bad arguments or a failed allocation: nothing is launched)
+    int execute(const cpx<T>* x, long long x_pitch, cpx<T>* y, long long y_pitch) {
+        if (!ok || !x || !y) return -1;
+        const long long xm = (long long)rows * cols, ym = (long long)out_rows * out_cols;
+        if (x_pitch == 0) x_pitch = xm;
+        if (y_pitch == 0) y_pitch = ym;
+        if (x_pitch < xm || y_pitch < ym) return -1;
+        const int M = n_matrices;
+        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)((long long)(M - 1) * x_pitch + xm) * SZ;
+        const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (size_t)((long long)(M - 1) * y_pitch + ym) * SZ;
+        if (x0 < y1 && y0 < x1) return -1;
+        const unsigned per_block = 256 * BLU_PER_THREAD;
+        if (fused()) {
+            const unsigned bpr_q = (unsigned)(((long long)Q + per_block - 1) / per_block);
+            // 1: rows forward, x -> work1 [M][rows][Q]
+            const bool x_contig = x_pitch == xm, y_contig = y_pitch == ym;
+            if ((x0 & 15) == 0 && (x_contig || (x_pitch % V) == 0)) {
+                ExecHooks<T> f;
+                f.n_in = cols; f.in_pitch = cols;
+                if (x_contig) {
+                    rowp.execute_hooked(x, work1, rows * M, false, f);
+                } else {
+                    for (int m = 0; m < M; m++) rowp.execute_hooked(x + (long long)m * x_pitch, work1 + (size_t)m * rows * Q, rows, false, f);
+                }
+            } else {
+                for (int m = 0; m < M; m++)
+                    rt->launch(fftk::pad_mul_kernel<T>, (long long)bpr_q * rows, 256, (size_t)0, x + (long long)m * x_pitch, (long long)cols, cols,
+                               (const cpx<T>*)nullptr, (int)fftk::HOOK_NONE, work1 + (size_t)m * rows * Q, Q, bpr_q);
+                rowp.execute(work1, work1, rows * M, false);
+            }
+            // 2: column round, work1 -> work2 [M][out_rows][Q]
+            round.run(work1, rows, H, work2, out_rows, M);
+            // 3: rows inverse, work2 -> y
+            if ((y0 & 15) == 0 && (y_contig || (y_pitch % V) == 0)) {
+                ExecHooks<T> g;
+                g.n_out = out_cols; g.out_pitch = out_cols;
+                if (y_contig) {
+                    rowp.execute_hooked(work2, y, out_rows * M, true, g);
+                } else {
+                    for (int m = 0; m < M; m++) rowp.execute_hooked(work2 + (size_t)m * out_rows * Q, y + (long long)m * y_pitch, out_rows, true, g);
+                }
+            } else {
+                rowp.execute(work2, work2, out_rows * M, true);
+                const unsigned bpr_o = (unsigned)(((long long)out_cols + per_block - 1) / per_block);
+                for (int m = 0; m < M; m++)
+                    rt->launch(fftk::mul_store_kernel<T>, (long long)bpr_o * out_rows, 256, (size_t)0, (const cpx<T>*)(work2 + (size_t)m * out_rows * Q), (long long)Q,
+                               (const cpx<T>*)nullptr, 0ll, (int)fftk::HOOK_NONE, y + (long long)m * y_pitch, (long long)out_cols, out_cols, (T)1, bpr_o);
+            }
+            return 0;
+        }
+        if (!ensure_fallback()) return -1;
+        const long long pq = (long long)P * Q;
+        const int log2P = ilog2(P), log2Q = ilog2(Q);
+        launch_flat(rt, fftk::conv2d_pad_kernel<T>, pq * M, x, x_pitch, rows, cols, fwork, log2P, log2Q, pq * M);
+        fwd->execute(fwork, fwork, M);
+        const unsigned bpr = (unsigned)((pq + per_block - 1) / per_block);
+        rt->launch(fftk::mul_store_kernel<T>, (long long)bpr * M, 256, (size_t)0, (const cpx<T>*)fwork, pq, (const cpx<T>*)H, 0ll, (int)fftk::HOOK_MUL, fwork, pq,
+                   (int)pq, (T)1, bpr);
+        inv->execute(fwork, fwork, M);
+        launch_flat(rt, fftk::conv2d_crop_kernel<T>, ym * M, (const cpx<T>*)fwork, log2P, log2Q, y, y_pitch, out_rows, out_cols, ym * M);
         return 0;
     }
 };

@@ -76,6 +76,9 @@ SIGNATURES = {
     "fft_gpu_execute_cross_frames_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_double]),
     "fft_gpu_plan_filter_hip": (_vp, [_i, _vp, _i, _i, _i, _i, _i]), "fft_gpu_filter_out_len_hip": (_i, [_vp]),
     "fft_gpu_filter_block_hip": (_i, [_vp]), "fft_gpu_execute_filter_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_conv2d_hip": (_vp, [_i, _i, _i, _i, _vp, _i, _i, _i]), "fft_gpu_conv2d_out_rows_hip": (_i, [_vp]),
+    "fft_gpu_conv2d_out_cols_hip": (_i, [_vp]), "fft_gpu_conv2d_padded_rows_hip": (_i, [_vp]), "fft_gpu_conv2d_padded_cols_hip": (_i, [_vp]),
+    "fft_gpu_execute_conv2d_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -107,6 +110,9 @@ SIGNATURES = {
     # include/fft_gpu.h, behind its include of fft_hip.h
     "fft_gpu_plan_filter": (_vp, [_i, _vp, _i, _i, _i, _i, _i]), "fft_gpu_filter_out_len": (_i, [_vp]),
     "fft_gpu_filter_block": (_i, [_vp]), "fft_gpu_execute_filter": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_conv2d": (_vp, [_i, _i, _i, _i, _vp, _i, _i, _i]), "fft_gpu_conv2d_out_rows": (_i, [_vp]),
+    "fft_gpu_conv2d_out_cols": (_i, [_vp]), "fft_gpu_conv2d_padded_rows": (_i, [_vp]), "fft_gpu_conv2d_padded_cols": (_i, [_vp]),
+    "fft_gpu_execute_conv2d": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -124,6 +130,7 @@ SIGNATURES = {
     "fft_coherence_real_gpu": (_vp, [_vp, _vp, _i, _i, _i]), "fft_csd_real_gpu": (_i, [_vp, _vp, _i, C.c_double, _i, _i, _vp]),
     "fft_fir_filter_gpu": (_i, [_vp, _i, _vp, _i, _vp]),
     "fft_design_fir_filter_gpu": (_vp, [_i, _i, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "fft_convolution_2d_gpu": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]), "fft_filter_2d_gpu": (_i, [_vp, _i, _i, _vp, _vp]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -430,6 +437,27 @@ class ExtPlan:
         p.block = p.lib.fft_gpu_filter_block_hip(p.handle)
         return p
 
+    @classmethod
+    def conv2d(cls, k, rows, cols, n_matrices=1, mode="full", dtype=np.complex128):
+        """2D convolution plan (fft_gpu_plan_conv2d_hip): n_matrices row-major rows x cols complex images, the kernel k ([krows, kcols]),
+        the output of CONV2D_MODES[mode] ("full", "same", "valid": scipy.signal.convolve2d's; "circular": the kernel wraps, sizes powers of
+        two; "spectrum": k IS the rows x cols spectrum H in natural order, out = ifft2(fft2(x) * H)).  out_rows, out_cols: what the plan
+        writes per matrix; padded: (P, Q)."""
+        dt = np.dtype(dtype)
+        kk = np.ascontiguousarray(np.asarray(k).astype(dt))
+        if kk.ndim != 2:
+            raise ValueError("the kernel is a 2D array")
+        p = cls(init().fft_gpu_plan_conv2d_hip(rows, cols, kk.shape[0], kk.shape[1], kk.ctypes.data if kk.size else None, n_matrices, CONV2D_MODES[mode],
+                                               _prec_of(dt)))
+        p.n_matrices, p.rows, p.cols, p.mode, p.dtype = n_matrices, rows, cols, mode, dt
+        p.out_rows, p.out_cols = p.lib.fft_gpu_conv2d_out_rows_hip(p.handle), p.lib.fft_gpu_conv2d_out_cols_hip(p.handle)
+        p.padded = (p.lib.fft_gpu_conv2d_padded_rows_hip(p.handle), p.lib.fft_gpu_conv2d_padded_cols_hip(p.handle))
+        return p
+
+    def execute_conv2d(self, d_x, d_y, x_pitch=0, y_pitch=0):
+        if self.lib.fft_gpu_execute_conv2d_hip(self.handle, d_x, x_pitch, d_y, y_pitch) != 0:
+            raise RuntimeError("fft_gpu_execute_conv2d_hip failed")
+
     def execute_filter(self, d_x, d_y, x_pitch=0, y_pitch=0):
         if self.lib.fft_gpu_execute_filter_hip(self.handle, d_x, x_pitch, d_y, y_pitch) != 0:
             raise RuntimeError("fft_gpu_execute_filter_hip failed")
@@ -611,6 +639,52 @@ def fir_filter(x, h, mode="full", n=0, plan=None):
     return res[0] if x.ndim == 1 else res
 
 
+def conv2d(x, k, mode="full", plan=None):
+    """x: [matrices, rows, cols] (or [rows, cols]) complex64 / complex128 images, k: [krows, kcols] -> every image convolved with k on
+    the device (ExtPlan.conv2d).  mode "full", "same", "valid": scipy.signal.convolve2d(x, k, mode); "circular": rows and cols powers of
+    two, the kernel (no larger than the image) wraps.  plan: an ExtPlan.conv2d to reuse (k and mode are then the plan's).  Convenience: a
+    float32 / float64 x with a real k is widened to complex and the real part of the result is returned."""
+    x = np.asarray(x)
+    real = x.dtype in (np.dtype(np.float32), np.dtype(np.float64))
+    if real and k is not None and np.iscomplexobj(k):
+        raise ValueError("a real image takes a real kernel")
+    if real:
+        x = x.astype(np.complex64 if x.dtype == np.float32 else np.complex128)
+    if x.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)) or x.ndim not in (2, 3):
+        raise ValueError("conv2d takes [rows, cols] or [matrices, rows, cols] float32, float64, complex64 or complex128 images")
+    x = np.ascontiguousarray(x)
+    x3 = x.reshape((1,) + x.shape) if x.ndim == 2 else x
+    own = plan is None
+    if own:
+        plan = ExtPlan.conv2d(k, x3.shape[1], x3.shape[2], x3.shape[0], mode, x3.dtype)
+    elif (plan.n_matrices, plan.rows, plan.cols, plan.dtype) != (x3.shape[0], x3.shape[1], x3.shape[2], x3.dtype):
+        raise ValueError("the plan was made for another shape or precision")
+    shape = (x3.shape[0], plan.out_rows, plan.out_cols)
+    a, o = DeviceBuffer(x3.nbytes), DeviceBuffer(shape[0] * shape[1] * shape[2] * x3.dtype.itemsize)
+    try:
+        a.upload(x3)
+        plan.execute_conv2d(a.ptr, o.ptr, 0, 0)
+        if plan.sync() != 0:
+            raise RuntimeError("execute failed")
+        res = o.download(shape, x3.dtype)
+    finally:
+        a.free()
+        o.free()
+        if own:
+            plan.destroy()
+    if real:
+        res = np.ascontiguousarray(res.real)
+    return res[0] if x.ndim == 2 else res
+
+
+def filter2d(x, H):
+    """x: [matrices, rows, cols] (or [rows, cols]) complex images, rows and cols powers of two; H: [rows, cols] spectrum in natural
+    (unshifted) order, DC at [0, 0] -> ifft2(fft2(x) * H) on the device (ExtPlan.conv2d in "spectrum" mode).  A mask written in the
+    centred layout goes through np.fft.ifftshift first."""
+    return conv2d(x, H, "spectrum")
+
+
+CONV2D_MODES = {"full": 0, "same": 1, "valid": 2, "circular": 3, "spectrum": 4}
 FIR_TYPES = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3, "custom": 4}
 
 

@@ -1,7 +1,8 @@
 /*
  * fft_apps.c -- host-array front ends of the fused consumers (include/fft_apps.h): the reference's
  * applications/convolution.c:34-96 and applications/power_spectrum.c:58-86, 133-190 as one fused device plan each, and
- * applications/fft_filtering.c's FIR design with FIR filtering of a long signal as one overlap-save filter plan.
+ * applications/fft_filtering.c's FIR design with FIR filtering of a long signal as one overlap-save filter plan, and the 2D
+ * convolution applications/convolution.c:99-109 leaves as a placeholder with image_fft.c's spectrum masking as one 2D convolution plan.
  */
 #include <math.h>
 #include <stdio.h>
@@ -272,4 +273,62 @@ complex_t* fft_design_fir_filter_gpu(int taps, int type, double cutoff_low, doub
         return NULL;
     }
     return h;
+}
+
+/* one 2D convolution plan on host arrays: x (rows x cols, row-major) -> y (out_rows x out_cols) */
+static int run_conv2d(const complex_t* x, int rows, int cols, const complex_t* k, int krows, int kcols, fft_gpu_conv2d_t mode, complex_t* y) {
+    if (ensure_gpu() != 0) return -1;
+    int rc = -1;
+    fft_gpu_plan_t plan = fft_gpu_plan_conv2d_hip(rows, cols, krows, kcols, k, 1, mode, FFT_PREC_F64);
+    const size_t nx = (size_t)rows * (size_t)cols;
+    const size_t ny = plan ? (size_t)fft_gpu_conv2d_out_rows_hip(plan) * (size_t)fft_gpu_conv2d_out_cols_hip(plan) : 0;
+    fft_gpu_memory_t dx = plan ? fft_gpu_alloc(nx) : NULL;
+    fft_gpu_memory_t dy = plan ? fft_gpu_alloc(ny) : NULL;
+    if (plan && dx && dy) {
+        if (fft_gpu_copy_h2d_bytes_hip(dx, x, nx * sizeof(complex_t)) == 0 &&
+            fft_gpu_execute_conv2d_hip(plan, fft_gpu_memory_ptr(dx), 0, fft_gpu_memory_ptr(dy), 0) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+            fft_gpu_copy_d2h_bytes_hip(y, dy, ny * sizeof(complex_t)) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(dx);
+    fft_gpu_free(dy);
+    fft_gpu_destroy_plan(plan);
+    return rc;
+}
+
+int fft_convolution_2d_gpu(complex_t** image, int rows, int cols, complex_t** kernel, int krows, int kcols, complex_t** result) {
+    if (!image || !kernel || !result || rows <= 0 || cols <= 0 || krows <= 0 || kcols <= 0) return -1;
+    const long long orows = (long long)rows + krows - 1, ocols = (long long)cols + kcols - 1;
+    if (orows * ocols > (1ll << 30)) return -1;
+    complex_t* x = allocate_complex_array(rows * cols);
+    complex_t* k = allocate_complex_array(krows * kcols);
+    complex_t* y = allocate_complex_array((int)(orows * ocols));
+    int rc = -1;
+    if (x && k && y) {
+        for (int i = 0; i < rows; i++)
+            for (int j = 0; j < cols; j++) x[(size_t)i * cols + j] = image[i][j];
+        for (int i = 0; i < krows; i++)
+            for (int j = 0; j < kcols; j++) k[(size_t)i * kcols + j] = kernel[i][j];
+        rc = run_conv2d(x, rows, cols, k, krows, kcols, FFT_GPU_CONV2D_FULL, y);
+        if (rc == 0)
+            for (long long i = 0; i < orows; i++)
+                for (long long j = 0; j < ocols; j++) result[i][j] = y[i * ocols + j];
+    }
+    if (x) free_complex_array(x);
+    if (k) free_complex_array(k);
+    if (y) free_complex_array(y);
+    return rc;
+}
+
+int fft_filter_2d_gpu(const complex_t* image, int rows, int cols, const complex_t* H_centred, complex_t* out) {
+    if (!image || !H_centred || !out || rows <= 0 || cols <= 0 || !is_power_of_two(rows) || !is_power_of_two(cols)) return -1;
+    if ((long long)rows * cols > (1ll << 30)) return -1;
+    complex_t* H = allocate_complex_array(rows * cols);
+    if (!H) return -1;
+    /* fft_shift_2d puts bin (u, v) at [(u + rows/2) mod rows][(v + cols/2) mod cols]: undo it */
+    for (int u = 0; u < rows; u++)
+        for (int v = 0; v < cols; v++) H[(size_t)u * cols + v] = H_centred[(size_t)((u + rows / 2) % rows) * cols + (size_t)((v + cols / 2) % cols)];
+    const int rc = run_conv2d(image, rows, cols, H, rows, cols, FFT_GPU_CONV2D_SPECTRUM, out);
+    free_complex_array(H);
+    return rc;
 }

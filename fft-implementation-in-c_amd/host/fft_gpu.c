@@ -259,6 +259,26 @@ int fft_gpu_execute_filter(fft_gpu_plan_t plan, const void* d_x, long long x_pit
     return fft_gpu_execute_filter_hip(plan, d_x, x_pitch, d_y, y_pitch);
 }
 
+/* 2D convolution plans: convolution and spectrum filtering of images */
+fft_gpu_plan_t fft_gpu_plan_conv2d(int rows, int cols, int krows, int kcols, const void* k_host, int n_matrices, fft_gpu_conv2d_t mode,
+                                   fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_conv2d")) return NULL;
+    return fft_gpu_plan_conv2d_hip(rows, cols, krows, kcols, k_host, n_matrices, mode, prec);
+}
+
+int fft_gpu_conv2d_out_rows(fft_gpu_plan_t plan) { return fft_gpu_conv2d_out_rows_hip(plan); }
+
+int fft_gpu_conv2d_out_cols(fft_gpu_plan_t plan) { return fft_gpu_conv2d_out_cols_hip(plan); }
+
+int fft_gpu_conv2d_padded_rows(fft_gpu_plan_t plan) { return fft_gpu_conv2d_padded_rows_hip(plan); }
+
+int fft_gpu_conv2d_padded_cols(fft_gpu_plan_t plan) { return fft_gpu_conv2d_padded_cols_hip(plan); }
+
+int fft_gpu_execute_conv2d(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
+    if (!backend_is_hip("fft_gpu_execute_conv2d")) return -1;
+    return fft_gpu_execute_conv2d_hip(plan, d_x, x_pitch, d_y, y_pitch);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

@@ -60,6 +60,16 @@ int fft_fir_filter_gpu(const complex_t* x, int nx, const complex_t* h, int nh, c
  * inverse transform (on the device) shifted by taps / 2 and Hamming-windowed with the taps - 1 denominator.  taps >= 2.  A malloc'd
  * (allocate_complex_array) array of taps values freed by the caller; NULL on failure and without a device. */
 complex_t* fft_design_fir_filter_gpu(int taps, int type, double cutoff_low, double cutoff_high, double sample_rate, double transition_width);
+/* 2D linear convolution, the reference's fft_convolution_2d (applications/convolution.c:99-109, a placeholder there) with its signature:
+ * image and kernel as arrays of row pointers, result rows of (cols + kcols - 1) values, (rows + krows - 1) of them, allocated by the
+ * caller.  ONE 2D convolution plan (fft_gpu_plan_conv2d_hip, FULL).  0 / -1, -1 without a device. */
+int fft_convolution_2d_gpu(complex_t** image, int rows, int cols, complex_t** kernel, int krows, int kcols, complex_t** result);
+/* Frequency-domain filtering of a row-major rows x cols image (powers of two) with a mask in the CENTRED layout of the reference's
+ * fft_shift_2d, DC at [rows/2][cols/2] -- what image_fft.c's ideal low-pass, Gaussian and edge-detection masks are written in
+ * (applications/image_fft.c:147-235): out = IFFT2(FFT2(image) . unshift(H_centred)).  The mask is unshifted on the host and the plan runs
+ * in SPECTRUM mode.  The result carries ONE 1 / (rows cols), like the 2D plans; the reference's fft_2d divides twice
+ * (image_fft.c:64-71), so its filtered images are smaller by that factor.  0 / -1, -1 without a device. */
+int fft_filter_2d_gpu(const complex_t* image, int rows, int cols, const complex_t* H_centred, complex_t* out);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,14 @@ fft_gpu_plan_t fft_gpu_plan_filter(int n_taps, const void* h_host, int signal_le
 int fft_gpu_filter_out_len(fft_gpu_plan_t plan);
 int fft_gpu_filter_block(fft_gpu_plan_t plan);
 int fft_gpu_execute_filter(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch);
+/* 2D convolution plans (fft_gpu_plan_conv2d_hip, fft_hip.h) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_conv2d(int rows, int cols, int krows, int kcols, const void* k_host, int n_matrices, fft_gpu_conv2d_t mode,
+                                   fft_precision_t prec);
+int fft_gpu_conv2d_out_rows(fft_gpu_plan_t plan);
+int fft_gpu_conv2d_out_cols(fft_gpu_plan_t plan);
+int fft_gpu_conv2d_padded_rows(fft_gpu_plan_t plan);
+int fft_gpu_conv2d_padded_cols(fft_gpu_plan_t plan);
+int fft_gpu_execute_conv2d(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch);
 #ifdef __cplusplus
 }
 #endif

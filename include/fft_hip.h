@@ -303,6 +303,36 @@ int fft_gpu_filter_block_hip(fft_gpu_plan_t plan);     /* n actually used; -1: n
  * its row, d_y overlapping d_x (blocks re-read their neighbours' input: in place cannot work). */
 int fft_gpu_execute_filter_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch /* 0: signal_len */,
                                void* d_y, long long y_pitch /* 0: out_len */);
+/* 2D convolution and frequency-domain filtering of n_matrices row-major rows x cols complex images with ONE kernel fixed at plan time:
+ * out = IFFT2(FFT2(x zero padded to P x Q) . H).  The reference declares fft_convolution_2d and leaves a placeholder
+ * (applications/convolution.c:99-109); applications/image_fft.c:147-235 masks the 2D spectrum of an image.  P = next_pow2(rows + krows - 1),
+ * Q = next_pow2(cols + kcols - 1) for FULL / SAME / VALID; P = rows, Q = cols for CIRCULAR / SPECTRUM.  H is computed once at plan time (the
+ * kernel placed in a [P][Q] array, circularly shifted by the mode's output offset, transformed on the device).  The result carries one
+ * 1 / (P Q), like the 2D plans (the reference's fft_2d divides twice, image_fft.c:64-71).  Where the P rows of C columns fit one LDS tile
+ * with row segments of at least 64 bytes (P >= 8) and the rows of length Q run with fused ends, an execute is three launches and three HBM
+ * round trips of compact work images: row transforms of the rows image rows only, ONE kernel for forward columns . H . inverse columns,
+ * row transforms of the out_rows wanted rows straight into d_y.  Everything else, and FFT_GPU_OPT_NO_FUSION: pad, forward 2D plan,
+ * product, inverse 2D plan, crop -- five round trips of the padded image.  fft_gpu_plan_info_hip: n = Q, batch = n_matrices,
+ * factors = {Q, P, Q}, n_passes = 3 / 5, fused = 1 / 0.  NULL: non-positive sizes, P Q > 2^30, VALID with a kernel larger than the image,
+ * CIRCULAR / SPECTRUM with sizes that are no powers of two (CIRCULAR: a kernel larger than the image; SPECTRUM: krows != rows or
+ * kcols != cols), a failed allocation. */
+typedef enum { FFT_GPU_CONV2D_FULL = 0,      /* out (rows+krows-1) x (cols+kcols-1), scipy convolve2d 'full'          */
+               FFT_GPU_CONV2D_SAME = 1,      /* out rows x cols = full[(krows-1)/2 ..][(kcols-1)/2 ..]                */
+               FFT_GPU_CONV2D_VALID = 2,     /* out (rows-krows+1) x (cols-kcols+1); krows <= rows, kcols <= cols     */
+               FFT_GPU_CONV2D_CIRCULAR = 3,  /* rows, cols powers of two; kernel krows <= rows, kcols <= cols, wraps  */
+               FFT_GPU_CONV2D_SPECTRUM = 4   /* rows, cols powers of two; k_host IS H[rows][cols] in natural (unshifted)
+                                                order, krows = rows, kcols = cols: out = IFFT2(FFT2(x) . H)           */
+} fft_gpu_conv2d_t;
+fft_gpu_plan_t fft_gpu_plan_conv2d_hip(int rows, int cols, int krows, int kcols, const void* k_host /* complex of prec, row-major */,
+                                       int n_matrices, fft_gpu_conv2d_t mode, fft_precision_t prec);
+int fft_gpu_conv2d_out_rows_hip(fft_gpu_plan_t plan);     /* -1: not such a plan */
+int fft_gpu_conv2d_out_cols_hip(fft_gpu_plan_t plan);
+int fft_gpu_conv2d_padded_rows_hip(fft_gpu_plan_t plan);  /* P */
+int fft_gpu_conv2d_padded_cols_hip(fft_gpu_plan_t plan);  /* Q */
+/* async on the plan's stream.  Matrix m is read at d_x + m * x_pitch and written at d_y + m * y_pitch (elements); the elements between
+ * matrices are neither read nor written.  -1, nothing launched: NULL pointers, a pitch smaller than its matrix, d_y overlapping d_x. */
+int fft_gpu_execute_conv2d_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch /* elements between matrices, 0: rows*cols */,
+                               void* d_y, long long y_pitch /* 0: out_rows*out_cols */);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
