@@ -311,7 +311,7 @@ struct fft_gpu_plan {
     ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
     ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
     // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter, 9 2D convolution
+    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter, 9 2D convolution, 10 real 2D forward, 11 real 2D inverse
     int rows = 0, cols = 0;
     ffteng::Plan2D<float, HipRT>* d32 = nullptr;
     ffteng::Plan2D<double, HipRT>* d64 = nullptr;
@@ -329,9 +329,11 @@ struct fft_gpu_plan {
     ffteng::FilterPlan<double, HipRT>* s64 = nullptr;
     ffteng::Conv2DPlan<float, HipRT>* c32 = nullptr;  // 2D convolution / spectrum filtering of images
     ffteng::Conv2DPlan<double, HipRT>* c64 = nullptr;
+    ffteng::Real2DPlan<float, HipRT>* q32 = nullptr;  // rfft2 / irfft2 of real images
+    ffteng::Real2DPlan<double, HipRT>* q64 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11 };
 
 namespace {
 
@@ -448,6 +450,14 @@ void for_each_core(fft_gpu_plan* p, F&& f) {
         two(c->fwd); two(c->inv);
     };
     conv(p->c32); conv(p->c64);
+    auto real2d = [&](auto* q) {
+        if (!q) return;
+        if (q->core.ok) f(&q->core);
+        if (q->cstep.colp.ok) f(&q->cstep.colp);
+        if (q->rp) any(&q->rp->core);
+        any(q->colt);
+    };
+    real2d(p->q32); real2d(p->q64);
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -505,6 +515,7 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     else if (p->x32 || p->x64) return -1;  // cross frames plans take two signals: fft_gpu_execute_cross_frames_hip
     else if (p->s32 || p->s64) return -1;  // filter plans take two pitches: fft_gpu_execute_filter_hip
     else if (p->c32 || p->c64) return -1;  // 2D convolution plans take two pitches: fft_gpu_execute_conv2d_hip
+    else if (p->q32 || p->q64) return -1;  // real 2D plans take two pitches: fft_gpu_execute_real2d_hip
     else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
     else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
     else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
@@ -775,6 +786,8 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
         delete p->s64;
         delete p->c32;
         delete p->c64;
+        delete p->q32;
+        delete p->q64;
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -1183,6 +1196,48 @@ int fft_gpu_execute_conv2d_hip(fft_gpu_plan_t p, const void* d_x, long long x_pi
     return 0;
 }
 
+// real 2D transforms of row-major images, numpy's rfft2 / irfft2 (fft_plans_ext.h Real2DPlan)
+static fft_gpu_plan_t plan_real2d(int rows, int cols, int n_matrices, fft_precision_t prec, bool r2c) {
+    if (rows <= 0 || cols <= 0 || n_matrices <= 0 || (long long)rows * cols > (1ll << 30)) {
+        fprintf(stderr, "fft_hip: invalid real 2D plan arguments (rows=%d cols=%d matrices=%d)\n", rows, cols, n_matrices);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(cols, n_matrices, r2c ? -1 : 1, prec, r2c ? PLAN_R2C_2D : PLAN_C2R_2D);
+    if (!p) return NULL;
+    p->rows = rows; p->cols = cols;
+    bool ok;
+    if (prec == FFT_PREC_F32) {
+        p->q32 = new (std::nothrow) ffteng::Real2DPlan<float, HipRT>();
+        ok = p->q32 && p->q32->build(&p->rt, rows, cols, n_matrices, r2c);
+    } else {
+        p->q64 = new (std::nothrow) ffteng::Real2DPlan<double, HipRT>();
+        ok = p->q64 && p->q64->build(&p->rt, rows, cols, n_matrices, r2c);
+    }
+    return finish_plan(p, ok, r2c ? "real 2D forward" : "real 2D inverse");
+}
+fft_gpu_plan_t fft_gpu_plan_r2c_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec) { return plan_real2d(rows, cols, n_matrices, prec, true); }
+fft_gpu_plan_t fft_gpu_plan_c2r_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec) { return plan_real2d(rows, cols, n_matrices, prec, false); }
+int fft_gpu_real2d_bins_hip(fft_gpu_plan_t p) {
+    if (!p) return -1;
+    if (p->q32) return p->q32->hb;
+    if (p->q64) return p->q64->hb;
+    return -1;
+}
+// async on the plan's stream.  Forward: d_in the real images, d_out the one-sided spectra; inverse: the other way round.  Pitches in
+// elements of their own side between matrices (0: dense); the two buffers must not overlap
+int fft_gpu_execute_real2d_hip(fft_gpu_plan_t p, const void* d_in, long long in_pitch, void* d_out, long long out_pitch) {
+    if (!p || !d_in || !d_out || (!p->q32 && !p->q64)) return -1;
+    DeviceGuard guard(p->device);
+    const int rc = p->q32 ? p->q32->execute(d_in, in_pitch, d_out, out_pitch) : p->q64->execute(d_in, in_pitch, d_out, out_pitch);
+    if (rc != 0) return -1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
 int fft_gpu_plan_set_stream_hip(fft_gpu_plan_t p, void* hip_stream) {
     if (!p) return -1;
     (void)hipStreamSynchronize(p->rt.stream);
@@ -1431,7 +1486,10 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             if (p->s64) p->s64->no_fusion = value != 0;
             if (p->c32) p->c32->no_fusion = value != 0;
             if (p->c64) p->c64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64 || p->c32 || p->c64) ? 0 : -1;
+            if (p->q32) p->q32->no_fusion = value != 0;
+            if (p->q64) p->q64->no_fusion = value != 0;
+            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64 || p->c32 || p->c64 ||
+                    p->q32 || p->q64) ? 0 : -1;
         case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
             auto set = [&](auto* q) {
                 if (!q) return;
@@ -1619,6 +1677,24 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
     };
     if (p->c32) fill_conv2d(p->c32);
     if (p->c64) fill_conv2d(p->c64);
+    // real 2D: n = cols, batch = matrices, factors = {cols, rows}; n_passes = 2 launches fused, else the fallback's steps (the row plan;
+    // transpose, column plan, transpose); fused: 1 the hooked rows kernel and the column pass kernel run; algo / chunk_batch: the row core's
+    auto fill_real2d = [&](auto* q) {
+        if (q->fusable()) fill(&q->core);
+        else if (q->rp) { if (q->rp->core.p2) fill(q->rp->core.p2); else if (q->rp->core.bl) fill(&q->rp->core.bl->core); }
+        info->n = q->cols;
+        info->batch = q->n_matrices;
+        info->n_passes = q->passes();
+        info->factors[0] = q->cols; info->factors[1] = q->rows; info->factors[2] = 0; info->factors[3] = 0;
+        info->fused = q->fused() ? 1 : 0;
+        if (q->work) info->workspace_bytes += (size_t)q->n_matrices * (size_t)q->rows * (size_t)q->ld * sizeof(*q->work);
+        if (q->rout) info->workspace_bytes += q->real_bytes();
+        if (q->rstage) info->workspace_bytes += q->real_bytes();
+        if (q->fwork) info->workspace_bytes += q->spec_bytes();
+        if (q->tbuf) info->workspace_bytes += q->spec_bytes();
+    };
+    if (p->q32) fill_real2d(p->q32);
+    if (p->q64) fill_real2d(p->q64);
     // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
     auto fill_any = [&](auto* a) {
         if (a->p2) fill(a->p2);

@@ -1,13 +1,15 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
-// overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, and 2D convolution / spectrum filtering).  Templated on the same runtime policy RT as the engine, so the
+// overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, 2D convolution / spectrum filtering, and the real 2D
+// transforms rfft2 / irfft2).  Templated on the same runtime policy RT as the engine, so the
 // unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
 #include "fft_engine.h"
 #include "fft_kernels_ext.h"
 #include "fft_kernels_conv2d.h"
+#include "fft_kernels_real2d.h"
 
 namespace ffteng {
 
@@ -1183,6 +1185,266 @@ class CrossFramesPlan {
         const long long tp = S * chunks * hb;
         launch(fftk::frames_cross_partial_kernel<T>, tp, (const cpx<T>*)rows_x, (const cpx<T>*)rows_y, row_pitch, part, inner.nw, hb, C, chunks, tp);
         launch(fftk::frames_cross_finish_kernel<T>, S * hb, (const double*)part, (T*)out, inner.nw, hb, chunks, base, out_kind, S * hb);
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Real 2D transforms of row-major images, numpy's rfft2 / irfft2 (the reference's applications/image_fft.c:35-60 starts from real
+// pixels and widens them to complex by hand):
+//   forward  X = rfft2(x):  x [M][rows][cols] real -> X [M][rows][cols/2 + 1] complex, unscaled
+//   inverse  x = irfft2(X, s = (rows, cols)): a full complex inverse transform along the columns of all cols/2 + 1 columns, then a c2r
+//            along the rows (which ignores the imaginary parts of bins 0 and -- even cols -- cols/2 of every row, like numpy.fft.irfft),
+//            scaled ONCE by 1 / (rows * cols), like Plan2D: irfft2(rfft2(x)) = x, and input that is not Hermitian-consistent gives
+//            what numpy gives.
+// Matrices lie in_pitch / out_pitch elements apart (reals on the real side, complex values on the spectral side; 0: dense); the rows
+// of a matrix are dense.  Input and output must not overlap; the input is never written.
+//
+// Fused path: two launches on half-size data.  L = cols/2, hb = L + 1, P = rows.
+//   forward  1  rows     ONE launch of the hooked single-pass rows kernel over rows * M frames of cols reals (tile_fft_kernel HOOK bit 6:
+//                        packed real load where the image lies -- any base, any matrix pitch -- r2c split in the store) -> the one-sided
+//                        rows of the work image [M][rows][ld], ld = L + V: its rows are 16-byte aligned
+//            2  columns  tile_fft_colpass_kernel over hb live columns: 16-byte loads from the work image, stores straight into the
+//                        caller's [M][rows][hb] (value by value in fp32, where those rows are only 8-byte aligned)
+//   inverse  1  columns  tile_fft_colpass_kernel, inverse, scale 1 / P: the caller's X (value by value in fp32) -> work image
+//                        [M][rows][hb] -- the pitch the Hermitian rows load reads (ExecHooks::herm_rows fixes it at L + 1)
+//            2  rows     ONE launch of the hooked rows kernel with HOOK bit 7, inverse, scale 1 / L -> the real rows, straight into the
+//                        caller's x where that is dense and 16-byte aligned; otherwise into an image of the plan's own and from there
+//                        by real2d_copy_kernel (a third launch: the rows kernel stores 16 bytes at a time)
+// taken where cols is a power of two whose half fits ONE hook-capable pass (FramesPlan's criterion: core.round_capable() and
+// frames_exact(), up to kLmax), rows is a power of two with a one-pass column tile of E = 8 (rows >= 8) and row segments of at least
+// min_seg_bytes = 64 bytes (ColRoundStep's criterion).
+// Fallback (everything else and no_fusion; correct, not tuned): RealPlan on the rows (odd cols: its promoted path), then -- rows > 1 --
+// transpose_kernel, AnyPlan of length rows on the hb * M transposed columns, transpose_kernel; the inverse runs the same steps in
+// reverse, and real2d_real_ends_kernel first zeroes the imaginary parts a c2r ignores (RealPlan's merge reads them).  Everything goes through images of the plan's own (the input stays untouched, RealPlan sees dense 16-byte aligned rows);
+// real2d_copy_kernel moves matrices to or from a caller's buffer that has a pitch of its own or is not 16-byte aligned.  Its plans
+// and images are made at the first execute that needs them.
+// ---------------------------------------------------------------------------
+
+// one run of the column stages as a step of its own: P rows, n_cols live columns, separate pitches on the two sides
+template <typename T, typename RT>
+class ColPassStep {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    RT* rt = nullptr;
+    Pow2Plan<T, RT> colp;  // build_columns: the tile and the stage tables
+    int log2P = 0, n_cols = 0, n_ct = 0;
+    bool ok = false;
+    // the tile is that of the n_cols - 1 columns before the last (rounded down to the 16-byte lane access): for the L + 1 columns of
+    // a real image's row spectra C divides L, and the last tile of every matrix holds exactly one live column
+    bool build(RT* runtime, int log2P_, int n_cols_, int n_matrices, int min_seg_bytes) {
+        rt = runtime; log2P = log2P_; n_cols = n_cols_;
+        int tc = (n_cols - 1) / V * V;
+        if (tc < V) tc = V;
+        if (n_cols < 1 || !colp.build_columns(rt, log2P, tc, n_matrices)) return false;
+        const PassDesc& a = colp.passes[0];
+        n_ct = (int)((n_cols + (1ll << a.log2C) - 1) >> a.log2C);
+        ok = a.E == 8 && a.log2H == 0 && a.nthreads <= 512 && a.seg_bytes >= min_seg_bytes;
+        return ok;
+    }
+    int tile_cols() const { return ok ? 1 << colp.passes[0].log2C : 0; }
+    // out[m][K][c] = scale * sum_l in[m][l][c] W_P^(+-K l), c < n_cols.  vec: base, row pitch and matrix pitch of that side are
+    // multiples of 16 bytes
+    void run(const cpx<T>* in, long long in_ld, long long in_b, bool in_vec, cpx<T>* out, long long out_ld, long long out_b, bool out_vec, int nm,
+             bool inverse, T scale) {
+        const PassDesc& a = colp.passes[0];
+        fftk::ColPassParams<T> q;
+        memset(&q, 0, sizeof(q));
+        q.in = in; q.out = out; q.tables = colp.pass_tables[0];
+        q.group_bytes = a.group_bytes; q.tables_bytes = a.tables_elems * SZ; q.off_tables = a.off_tables; q.o_sb = a.o_sb; q.sa_bits = a.sa_bits;
+        q.log2L = a.log2L; q.log2C = a.log2C; q.n_ct = n_ct; q.n_cols = n_cols;
+        q.in_b = in_b; q.out_b = out_b; q.in_ld = in_ld; q.out_ld = out_ld;
+        q.n_tiles = (long long)nm * n_ct;
+        q.in_vec = in_vec ? 1 : 0; q.out_vec = out_vec ? 1 : 0;
+        q.inverse = inverse ? 1 : 0;
+        q.nt = a.seg_bytes >= 128 ? 3 : 0;  // the tile passes' rule (Pow2Plan::pass_params): whole 128-byte lines only; not measured here
+        q.scale = scale;
+        int per_cu = rt->max_blocks_per_cu(fftk::tile_fft_colpass_kernel<T>, a.nthreads, (size_t)a.smem_bytes);
+        if (per_cu < 1) per_cu = 1;
+        long long grid = (long long)rt->num_cus() * per_cu;
+        if (grid > q.n_tiles) grid = q.n_tiles;
+        rt->launch(fftk::tile_fft_colpass_kernel<T>, grid, a.nthreads, (size_t)a.smem_bytes, q);
+    }
+};
+
+template <typename T, typename RT>
+class Real2DPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    // the longest half-row the fused path takes: what the hooked rows kernel's bits 6 and 7 are checked at (the real frames plans' tests
+    // stop at frames of 8192 reals in fp32, 4096 in fp64).  A device whose LDS holds one pass of 4096 fp64 points still takes the
+    // fallback there, as FilterPlan does beyond its kNmax
+    static constexpr int kLmax = SZ == 8 ? 4096 : 2048;
+    RT* rt = nullptr;
+    int rows = 0, cols = 0, n_matrices = 0;
+    bool forward = true;           // r2c
+    int L = 0, hb = 0;             // cols / 2, cols / 2 + 1
+    long long ld = 0;              // fused: elements between the rows of the work image
+    Pow2Plan<T, RT> core;          // fused: length L, hooked
+    ColPassStep<T, RT> cstep;
+    cpx<T>* wtab = nullptr;        // fused: W_cols^k, k <= L (the split's / merge's table)
+    cpx<T>* work = nullptr;        // fused: [M][rows][ld]
+    T* rout = nullptr;             // fused inverse: [M][rows][cols] for a caller's x the rows kernel cannot store to (made at its first use)
+    RealPlan<T, RT>* rp = nullptr; // fallback (made at its first use)
+    AnyPlan<T, RT>* colt = nullptr;
+    cpx<T>* fwork = nullptr;       // fallback: [M][rows][hb]
+    cpx<T>* tbuf = nullptr;        // fallback: [M][hb][rows]
+    T* rstage = nullptr;           // fallback: [M][rows][cols] (made at its first use)
+    int min_seg_bytes = 64;        // the fused path's row-segment criterion (tests narrow it to reach narrow tiles)
+    bool ok = false;
+    bool no_fusion = false;
+    ~Real2DPlan() {
+        delete rp;
+        delete colt;
+        if (!rt) return;
+        rt->dfree(wtab); rt->dfree(work); rt->dfree(rout); rt->dfree(fwork); rt->dfree(tbuf); rt->dfree(rstage);
+    }
+    long long frames() const { return (long long)rows * n_matrices; }
+    bool fusable() const { return ok && cstep.ok && core.ok && core.round_capable() && core.frames_exact(frames(), rows) && work && wtab; }
+    bool fused() const { return fusable() && !no_fusion; }
+    // what fft_gpu_plan_info_hip reports: 2 launches fused; on the fallback its steps (the row plan; transpose, column plan, transpose;
+    // the copies and the inverse's zeroing of the ignored imaginary parts are not counted)
+    int passes() const { return fused() ? 2 : rows > 1 ? 4 : 1; }
+    size_t real_bytes() const { return (size_t)n_matrices * (size_t)rows * (size_t)cols * sizeof(T); }
+    size_t spec_bytes() const { return (size_t)n_matrices * (size_t)rows * (size_t)hb * SZ; }
+
+    bool build(RT* runtime, int rows_, int cols_, int n_matrices_, bool r2c, int min_seg = 64) {
+        rt = runtime; rows = rows_; cols = cols_; n_matrices = n_matrices_; forward = r2c; min_seg_bytes = min_seg;
+        if (rows < 1 || cols < 1 || n_matrices < 1 || (long long)rows * cols > (1ll << 30) || (long long)rows * n_matrices > 0x7fffffff ||
+            (long long)cols * n_matrices > 0x7fffffff) return false;
+        L = cols / 2; hb = L + 1;
+        ok = true;
+        const bool p2 = (rows & (rows - 1)) == 0 && (cols & (cols - 1)) == 0;
+        if (p2 && rows >= 8 && cols >= 4 && L >= V && L <= kLmax && cstep.build(rt, ilog2(rows), hb, n_matrices, min_seg_bytes)) {
+            core.wants_hooks = true;
+            if (core.build(rt, ilog2(L), ALGO_AUTO, (int)frames()) && core.round_capable() && core.frames_exact(frames(), rows)) {
+                // forward: the rows kernel writes at any pitch, so the rows of the work image are 16-byte aligned; inverse: the
+                // Hermitian rows load reads rows of L + 1 bins and nothing else
+                ld = forward ? (long long)L + V : (long long)hb;
+                std::vector<cpx<T>> t;
+                make_twiddle_table<T>(t, cols, (long long)L + 1, 1);
+                wtab = (cpx<T>*)rt->dmalloc(t.size() * SZ);
+                work = (cpx<T>*)rt->dmalloc((size_t)n_matrices * (size_t)rows * (size_t)ld * SZ);
+                if (!wtab || !work) { ok = false; return false; }
+                rt->h2d(wtab, t.data(), t.size() * SZ);
+            }
+        }
+        if (!fusable() && !ensure_fallback()) { ok = false; return false; }
+        return true;
+    }
+
+    bool ensure_fallback() {
+        if (!rp) {
+            rp = new RealPlan<T, RT>();
+            if (!rp->build(rt, cols, forward, (int)frames())) { delete rp; rp = nullptr; return false; }
+        }
+        if (!fwork) fwork = (cpx<T>*)rt->dmalloc(spec_bytes());
+        if (!fwork) return false;
+        if (rows > 1) {
+            if (!colt) {
+                colt = new AnyPlan<T, RT>();
+                if (!colt->build(rt, rows, forward ? -1 : 1, hb * n_matrices)) { delete colt; colt = nullptr; return false; }
+            }
+            if (!tbuf) tbuf = (cpx<T>*)rt->dmalloc(spec_bytes());
+            if (!tbuf) return false;
+        }
+        return true;
+    }
+
+    template <typename E>
+    void copy(const E* src, long long src_pitch, E* dst, long long dst_pitch, long long per) {
+        launch_flat(rt, fftk::real2d_copy_kernel<E>, per * n_matrices, src, src_pitch, dst, dst_pitch, per, per * n_matrices);
+    }
+    void transpose(const cpx<T>* in, cpx<T>* out, int r, int c) {
+        const long long tiles = (long long)n_matrices * ((r + 31) / 32) * ((c + 31) / 32);
+        const long long grid = tiles > 65536 ? 65536 : tiles;
+        rt->launch(fftk::transpose_kernel<T>, grid, 256, (size_t)(32 * 33 * SZ), in, out, r, c, tiles);
+    }
+
+    // forward: in = x (reals), out = X; inverse: in = X, out = x.  Pitches in elements of their own side; 0: dense.  0 / -1 (the
+    // wrong direction, bad arguments or a failed allocation: nothing is launched)
+    int execute(const void* in, long long in_pitch, void* out, long long out_pitch) {
+        if (!ok || !in || !out) return -1;
+        const long long rm = (long long)rows * cols, sm = (long long)rows * hb;
+        const long long im = forward ? rm : sm, om = forward ? sm : rm;
+        const size_t isz = forward ? sizeof(T) : (size_t)SZ, osz = forward ? (size_t)SZ : sizeof(T);
+        if (in_pitch == 0) in_pitch = im;
+        if (out_pitch == 0) out_pitch = om;
+        if (in_pitch < im || out_pitch < om) return -1;
+        const int M = n_matrices;
+        const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)((long long)(M - 1) * in_pitch + im) * isz;
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)((long long)(M - 1) * out_pitch + om) * osz;
+        if (i0 < o1 && o0 < i1) return -1;
+        const bool in_dense = in_pitch == im, out_dense = out_pitch == om;
+        const T* x_in = (const T*)in;
+        const cpx<T>* X_in = (const cpx<T>*)in;
+        T* x_out = (T*)out;
+        cpx<T>* X_out = (cpx<T>*)out;
+        if (fused()) {
+            if (forward) {
+                ExecHooks<T> f;
+                f.n_in = L; f.in_pitch = cols;
+                f.frames_per_signal = rows; f.signal_pitch = in_pitch;
+                f.real_frames = true; f.post_tab = wtab; f.out_pitch = ld;
+                core.execute_frames(reinterpret_cast<const cpx<T>*>(x_in), work, (int)frames(), f);
+                const bool ovec = (o0 & 15) == 0 && (hb % V) == 0 && (out_pitch % V) == 0;  // fp64: every bin is 16 bytes
+                cstep.run(work, ld, (long long)rows * ld, true, X_out, hb, out_pitch, ovec, M, false, (T)1);
+            } else {
+                const bool direct = out_dense && (o0 & 15) == 0;
+                if (!direct && !rout) rout = (T*)rt->dmalloc(real_bytes());
+                if (!direct && !rout) return -1;
+                const bool ivec = (i0 & 15) == 0 && (hb % V) == 0 && (in_pitch % V) == 0;
+                cstep.run(X_in, hb, in_pitch, ivec, work, ld, (long long)rows * ld, (ld % V) == 0, M, true, (T)(1.0L / (long double)rows));
+                ExecHooks<T> g;
+                g.herm_rows = true;
+                g.pre_tab = wtab;
+                core.execute_iframes(work, reinterpret_cast<cpx<T>*>(direct ? x_out : rout), (int)frames(), g);
+                if (!direct) copy<T>(rout, rm, x_out, out_pitch, rm);
+            }
+            return 0;
+        }
+        if (!ensure_fallback()) return -1;
+        const int nf = (int)frames();
+        if (forward) {
+            const T* src = x_in;
+            if (!in_dense || (i0 & 15) != 0) {
+                if (!rstage) rstage = (T*)rt->dmalloc(real_bytes());
+                if (!rstage) return -1;
+                copy<T>(x_in, in_pitch, rstage, rm, rm);
+                src = rstage;
+            }
+            if (rows == 1) {
+                rp->execute_r2c(src, out_dense ? X_out : fwork, nf);
+            } else {
+                rp->execute_r2c(src, fwork, nf);
+                transpose(fwork, tbuf, rows, hb);
+                colt->execute(tbuf, tbuf, hb * M);
+                transpose(tbuf, out_dense ? X_out : fwork, hb, rows);
+            }
+            if (!out_dense) copy<cpx<T>>(fwork, sm, X_out, out_pitch, sm);
+        } else {
+            const bool direct = out_dense && (o0 & 15) == 0;
+            if (!direct && !rstage) rstage = (T*)rt->dmalloc(real_bytes());
+            if (!direct && !rstage) return -1;
+            if (rows > 1) {
+                const cpx<T>* src = X_in;
+                if (!in_dense) {
+                    copy<cpx<T>>(X_in, in_pitch, fwork, sm, sm);
+                    src = fwork;
+                }
+                transpose(src, tbuf, rows, hb);
+                colt->execute(tbuf, tbuf, hb * M);
+                transpose(tbuf, fwork, hb, rows);
+            } else {
+                copy<cpx<T>>(X_in, in_pitch, fwork, sm, sm);
+            }
+            // RealPlan's c2r uses the imaginary parts of bins 0 and cols/2 of a row; numpy's ignores them
+            launch_flat(rt, fftk::real2d_real_ends_kernel<T>, (long long)nf, fwork, hb, (cols & 1) == 0 ? 1 : 0, (long long)nf);
+            rp->execute_c2r(fwork, direct ? x_out : rstage, nf);
+            if (!direct) copy<T>(rstage, rm, x_out, out_pitch, rm);
+        }
         return 0;
     }
 };

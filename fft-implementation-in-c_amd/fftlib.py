@@ -79,6 +79,8 @@ SIGNATURES = {
     "fft_gpu_plan_conv2d_hip": (_vp, [_i, _i, _i, _i, _vp, _i, _i, _i]), "fft_gpu_conv2d_out_rows_hip": (_i, [_vp]),
     "fft_gpu_conv2d_out_cols_hip": (_i, [_vp]), "fft_gpu_conv2d_padded_rows_hip": (_i, [_vp]), "fft_gpu_conv2d_padded_cols_hip": (_i, [_vp]),
     "fft_gpu_execute_conv2d_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_r2c_2d_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_2d_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_real2d_bins_hip": (_i, [_vp]),
+    "fft_gpu_execute_real2d_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -113,6 +115,8 @@ SIGNATURES = {
     "fft_gpu_plan_conv2d": (_vp, [_i, _i, _i, _i, _vp, _i, _i, _i]), "fft_gpu_conv2d_out_rows": (_i, [_vp]),
     "fft_gpu_conv2d_out_cols": (_i, [_vp]), "fft_gpu_conv2d_padded_rows": (_i, [_vp]), "fft_gpu_conv2d_padded_cols": (_i, [_vp]),
     "fft_gpu_execute_conv2d": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_r2c_2d": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_2d": (_vp, [_i, _i, _i, _i]), "fft_gpu_real2d_bins": (_i, [_vp]),
+    "fft_gpu_execute_real2d": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -131,6 +135,7 @@ SIGNATURES = {
     "fft_fir_filter_gpu": (_i, [_vp, _i, _vp, _i, _vp]),
     "fft_design_fir_filter_gpu": (_vp, [_i, _i, C.c_double, C.c_double, C.c_double, C.c_double]),
     "fft_convolution_2d_gpu": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]), "fft_filter_2d_gpu": (_i, [_vp, _i, _i, _vp, _vp]),
+    "fft_rfft2_gpu": (_i, [_vp, _i, _i, _vp]), "fft_irfft2_gpu": (_i, [_vp, _i, _i, _vp]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -454,6 +459,27 @@ class ExtPlan:
         p.padded = (p.lib.fft_gpu_conv2d_padded_rows_hip(p.handle), p.lib.fft_gpu_conv2d_padded_cols_hip(p.handle))
         return p
 
+    @classmethod
+    def real2d(cls, rows, cols, n_matrices=1, inverse=False, dtype=np.float64):
+        """Real 2D transform plan (fft_gpu_plan_r2c_2d_hip / fft_gpu_plan_c2r_2d_hip): n_matrices row-major rows x cols real images of
+        dtype float32 / float64 and their one-sided spectra of rows x bins complex values, bins = cols // 2 + 1; numpy's rfft2, or with
+        inverse=True irfft2(X, s=(rows, cols)).  execute(d_in, d_out, in_pitch, out_pitch) runs it on device pointers."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("float32 or float64 expected")
+        prec = PREC_F32 if dt == np.float32 else PREC_F64
+        lib = init()
+        p = cls((lib.fft_gpu_plan_c2r_2d_hip if inverse else lib.fft_gpu_plan_r2c_2d_hip)(rows, cols, n_matrices, prec))
+        p.n_matrices, p.rows, p.cols, p.inverse, p.dtype = n_matrices, rows, cols, bool(inverse), dt
+        p.cdtype = np.dtype(np.complex64 if dt == np.float32 else np.complex128)
+        p.bins = p.lib.fft_gpu_real2d_bins_hip(p.handle)
+        p.execute = p.execute_real2d
+        return p
+
+    def execute_real2d(self, d_in, d_out, in_pitch=0, out_pitch=0):
+        if self.lib.fft_gpu_execute_real2d_hip(self.handle, d_in, in_pitch, d_out, out_pitch) != 0:
+            raise RuntimeError("fft_gpu_execute_real2d_hip failed")
+
     def execute_conv2d(self, d_x, d_y, x_pitch=0, y_pitch=0):
         if self.lib.fft_gpu_execute_conv2d_hip(self.handle, d_x, x_pitch, d_y, y_pitch) != 0:
             raise RuntimeError("fft_gpu_execute_conv2d_hip failed")
@@ -675,6 +701,46 @@ def conv2d(x, k, mode="full", plan=None):
     if real:
         res = np.ascontiguousarray(res.real)
     return res[0] if x.ndim == 2 else res
+
+
+def _real2d(a, rows, cols, inverse):
+    """a: [matrices, ...] contiguous input of one real 2D plan -> its output, through device buffers"""
+    M = a.shape[0]
+    plan = ExtPlan.real2d(rows, cols, M, inverse, np.float32 if a.dtype in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64)
+    shape, odt = ((M, rows, cols), plan.dtype) if inverse else ((M, rows, plan.bins), plan.cdtype)
+    d_in, d_out = DeviceBuffer(a.nbytes), DeviceBuffer(M * shape[1] * shape[2] * odt.itemsize)
+    try:
+        d_in.upload(a)
+        plan.execute_real2d(d_in.ptr, d_out.ptr, 0, 0)
+        if plan.sync() != 0:
+            raise RuntimeError("execute failed")
+        return d_out.download(shape, odt)
+    finally:
+        d_in.free()
+        d_out.free()
+        plan.destroy()
+
+
+def rfft2(x):
+    """x: [..., rows, cols] float32 / float64 images -> [..., rows, cols // 2 + 1] complex64 / complex128, numpy.fft.rfft2 over the last
+    two axes on the device (ExtPlan.real2d)."""
+    x = np.asarray(x)
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.float64)) or x.ndim < 2 or x.size == 0:
+        raise ValueError("rfft2 takes non-empty [..., rows, cols] float32 or float64 images")
+    rows, cols = x.shape[-2:]
+    res = _real2d(np.ascontiguousarray(x).reshape(-1, rows, cols), rows, cols, False)
+    return res.reshape(x.shape[:-1] + (cols // 2 + 1,))
+
+
+def irfft2(X, cols):
+    """X: [..., rows, cols // 2 + 1] complex64 / complex128 one-sided spectra -> [..., rows, cols] float32 / float64,
+    numpy.fft.irfft2(X, s=(rows, cols)) over the last two axes on the device: scaled by 1 / (rows cols), irfft2(rfft2(x), cols) = x."""
+    X = np.asarray(X)
+    if X.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)) or X.ndim < 2 or X.size == 0 or cols < 1 or X.shape[-1] != cols // 2 + 1:
+        raise ValueError("irfft2 takes non-empty [..., rows, cols // 2 + 1] complex64 or complex128 spectra")
+    rows = X.shape[-2]
+    res = _real2d(np.ascontiguousarray(X).reshape(-1, rows, X.shape[-1]), rows, cols, True)
+    return res.reshape(X.shape[:-2] + (rows, cols))
 
 
 def filter2d(x, H):

@@ -332,3 +332,34 @@ int fft_filter_2d_gpu(const complex_t* image, int rows, int cols, const complex_
     free_complex_array(H);
     return rc;
 }
+
+/* one real 2D plan on host arrays: `in` (in_bytes) -> `out` (out_bytes) */
+static int run_real2d(const void* in, size_t in_bytes, void* out, size_t out_bytes, int rows, int cols, int r2c) {
+    if (ensure_gpu() != 0) return -1;
+    int rc = -1;
+    fft_gpu_plan_t plan = r2c ? fft_gpu_plan_r2c_2d_hip(rows, cols, 1, FFT_PREC_F64) : fft_gpu_plan_c2r_2d_hip(rows, cols, 1, FFT_PREC_F64);
+    fft_gpu_memory_t din = plan ? fft_gpu_alloc_bytes_hip(in_bytes) : NULL;
+    fft_gpu_memory_t dout = plan ? fft_gpu_alloc_bytes_hip(out_bytes) : NULL;
+    if (plan && din && dout) {
+        if (fft_gpu_copy_h2d_bytes_hip(din, in, in_bytes) == 0 &&
+            fft_gpu_execute_real2d_hip(plan, fft_gpu_memory_ptr(din), 0, fft_gpu_memory_ptr(dout), 0) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+            fft_gpu_copy_d2h_bytes_hip(out, dout, out_bytes) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(din);
+    fft_gpu_free(dout);
+    fft_gpu_destroy_plan(plan);
+    return rc;
+}
+
+int fft_rfft2_gpu(const double* image, int rows, int cols, complex_t* out) {
+    if (!image || !out || rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 30)) return -1;
+    const size_t nr = (size_t)rows * (size_t)cols, ns = (size_t)rows * (size_t)(cols / 2 + 1);
+    return run_real2d(image, nr * sizeof(double), out, ns * sizeof(complex_t), rows, cols, 1);
+}
+
+int fft_irfft2_gpu(const complex_t* spec, int rows, int cols, double* image) {
+    if (!spec || !image || rows <= 0 || cols <= 0 || (long long)rows * cols > (1ll << 30)) return -1;
+    const size_t nr = (size_t)rows * (size_t)cols, ns = (size_t)rows * (size_t)(cols / 2 + 1);
+    return run_real2d(spec, ns * sizeof(complex_t), image, nr * sizeof(double), rows, cols, 0);
+}

@@ -279,6 +279,24 @@ int fft_gpu_execute_conv2d(fft_gpu_plan_t plan, const void* d_x, long long x_pit
     return fft_gpu_execute_conv2d_hip(plan, d_x, x_pitch, d_y, y_pitch);
 }
 
+/* real 2D plans, rfft2 / irfft2 (fft_hip.h) */
+fft_gpu_plan_t fft_gpu_plan_r2c_2d(int rows, int cols, int n_matrices, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_r2c_2d")) return NULL;
+    return fft_gpu_plan_r2c_2d_hip(rows, cols, n_matrices, prec);
+}
+
+fft_gpu_plan_t fft_gpu_plan_c2r_2d(int rows, int cols, int n_matrices, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_c2r_2d")) return NULL;
+    return fft_gpu_plan_c2r_2d_hip(rows, cols, n_matrices, prec);
+}
+
+int fft_gpu_real2d_bins(fft_gpu_plan_t plan) { return fft_gpu_real2d_bins_hip(plan); }
+
+int fft_gpu_execute_real2d(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch) {
+    if (!backend_is_hip("fft_gpu_execute_real2d")) return -1;
+    return fft_gpu_execute_real2d_hip(plan, d_in, in_pitch, d_out, out_pitch);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

@@ -70,6 +70,12 @@ int fft_convolution_2d_gpu(complex_t** image, int rows, int cols, complex_t** ke
  * in SPECTRUM mode.  The result carries ONE 1 / (rows cols), like the 2D plans; the reference's fft_2d divides twice
  * (image_fft.c:64-71), so its filtered images are smaller by that factor.  0 / -1, -1 without a device. */
 int fft_filter_2d_gpu(const complex_t* image, int rows, int cols, const complex_t* H_centred, complex_t* out);
+/* 2D transform of a REAL row-major rows x cols image and its inverse, numpy's rfft2 / irfft2 (applications/image_fft.c:35-60 widens the
+ * real pixels to complex by hand): out holds rows x (cols/2 + 1) bins, unscaled; fft_irfft2_gpu reads such a spectrum and writes the
+ * rows x cols image, scaled by 1 / (rows cols), so that fft_irfft2_gpu(fft_rfft2_gpu(x)) = x.  Host pointers; ONE real 2D plan each
+ * (fft_gpu_plan_r2c_2d_hip / fft_gpu_plan_c2r_2d_hip).  0 / -1, -1 without a device. */
+int fft_rfft2_gpu(const double* image, int rows, int cols, complex_t* out);
+int fft_irfft2_gpu(const complex_t* spec, int rows, int cols, double* image);
 
 #ifdef __cplusplus
 }

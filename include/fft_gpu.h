@@ -88,6 +88,11 @@ int fft_gpu_conv2d_out_cols(fft_gpu_plan_t plan);
 int fft_gpu_conv2d_padded_rows(fft_gpu_plan_t plan);
 int fft_gpu_conv2d_padded_cols(fft_gpu_plan_t plan);
 int fft_gpu_execute_conv2d(fft_gpu_plan_t plan, const void* d_x, long long x_pitch, void* d_y, long long y_pitch);
+/* real 2D plans, rfft2 / irfft2 (fft_gpu_plan_r2c_2d_hip, fft_hip.h) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_r2c_2d(int rows, int cols, int n_matrices, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_c2r_2d(int rows, int cols, int n_matrices, fft_precision_t prec);
+int fft_gpu_real2d_bins(fft_gpu_plan_t plan);
+int fft_gpu_execute_real2d(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
 #ifdef __cplusplus
 }
 #endif

@@ -333,6 +333,25 @@ int fft_gpu_conv2d_padded_cols_hip(fft_gpu_plan_t plan);  /* Q */
  * matrices are neither read nor written.  -1, nothing launched: NULL pointers, a pitch smaller than its matrix, d_y overlapping d_x. */
 int fft_gpu_execute_conv2d_hip(fft_gpu_plan_t plan, const void* d_x, long long x_pitch /* elements between matrices, 0: rows*cols */,
                                void* d_y, long long y_pitch /* 0: out_rows*out_cols */);
+/* Real 2D transforms of n_matrices row-major rows x cols real images, numpy's rfft2 / irfft2 (the reference's applications/image_fft.c
+ * starts from real pixels and widens them to complex by hand).  r2c: X = rfft2(x), [rows][cols/2 + 1] complex per image, unscaled.  c2r:
+ * x = irfft2(X, s = (rows, cols)): a full complex inverse transform along the columns of all cols/2 + 1 columns, then a c2r along the
+ * rows (which ignores the imaginary parts of bins 0 and, for even cols, cols/2 of every row, like numpy.fft.irfft), scaled once by
+ * 1 / (rows cols): irfft2(rfft2(x)) = x, and spectra that are not Hermitian-consistent give what numpy gives.  Where cols is a power of
+ * two whose half fits one single-pass row transform with fused ends and rows is a power of two >= 8 whose columns fit one LDS tile with
+ * row segments of at least 64 bytes, an execute is two launches on half-size data: the rows kernel (packed real load / r2c split, or
+ * c2r merge / real store) and ONE column kernel over the cols/2 + 1 one-sided columns.  Everything else, and FFT_GPU_OPT_NO_FUSION: the
+ * 1D real plan on the rows, transpose, a batched 1D plan of length rows, transpose.  fft_gpu_plan_info_hip: n = cols, batch =
+ * n_matrices, factors = {cols, rows}, n_passes = 2 fused (else the fallback's steps: 4, or 1 for a single row), fused = 1 / 0.
+ * NULL: non-positive sizes, rows cols > 2^30, rows n_matrices or cols n_matrices > 2^31 - 1, a failed allocation. */
+fft_gpu_plan_t fft_gpu_plan_r2c_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_c2r_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec);
+int fft_gpu_real2d_bins_hip(fft_gpu_plan_t plan);  /* cols/2 + 1; -1: not such a plan */
+/* async on the plan's stream.  r2c plans read reals at d_in + m * in_pitch and write complex values at d_out + m * out_pitch; c2r plans
+ * the other way round.  Pitches count elements of their own side between matrices (0: dense: rows * cols reals, rows * (cols/2 + 1)
+ * complex values); the rows of a matrix are dense; the elements between matrices are neither read nor written, and the input never is
+ * written.  -1, nothing launched: NULL pointers, a plan of another kind, a pitch smaller than its matrix, d_out overlapping d_in. */
+int fft_gpu_execute_real2d_hip(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
