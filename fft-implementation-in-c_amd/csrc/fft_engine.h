@@ -262,6 +262,9 @@ class Pow2Plan {
     bool ok = false;
 
     ~Pow2Plan() { destroy(); }
+    // each_core(f), here and in every plan class built on this one: f(core) for every Pow2Plan the plan runs transforms on -- what
+    // carries a team kernel's status to the handle (fft_gpu_plan_sync_hip) and the team options to the cores
+    template <class F> void each_core(F&& f) { f(this); }
 
     void destroy() {
         if (!rt) return;
@@ -1430,6 +1433,7 @@ class Pow2Plan {
     }
     static constexpr int kChainMinLog2n = 0;  // measured (tools/ab_chain.py, profiles/r2_ab_chain.txt): chaining wins at every size it applies to (2^14 ... 2^21: +7...27 %)
     int chain_min_log2n = kChainMinLog2n;
+    void set_chain_rule(bool everywhere) { chain_min_log2n = everywhere ? 0 : kChainMinLog2n; }
     bool chain_capable() const {
         if (!hook_capable() || passes.size() < 2 || log2n < chain_min_log2n) return false;
         if (mirror && !mirror->hook_capable()) return false;
@@ -1702,6 +1706,10 @@ class BluesteinPlan {
     bool ok = false;
     bool no_fusion = false;   // tests: run the element-wise steps as kernels of their own
     bool no_chain = false;    // tests: keep the forward transform's last and the inverse's first pass as two kernels
+    template <class F> void each_core(F&& f) { f(&core); }
+    void set_no_fusion(bool v) { no_fusion = v; }
+    // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
+    void set_no_chain(int v) { no_chain = v == 1; core.set_chain_rule(v == 2); }
 
     ~BluesteinPlan() {
         if (!rt) return;
@@ -1853,6 +1861,7 @@ class MixedRadixPlan {
     cpx<T>* scratch = nullptr;
     size_t scratch_bytes = 0;
     bool ok = false;
+    template <class F> void each_core(F&&) {}  // no power-of-two core: no team kernel
 
     ~MixedRadixPlan() {
         if (!rt) return;

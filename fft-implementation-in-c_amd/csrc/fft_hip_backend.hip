@@ -18,6 +18,7 @@
 #include <new>
 #include <set>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -299,38 +300,46 @@ struct fft_gpu_memory {
     int device;
 };
 
+// One member per plan kind, in one precision.  At most one member of one set is live in a handle: p->prec says which set, p->kind
+// which execute entry point the plan answers to.  each() is THE list of plan kinds: what destroys a handle, visits its cores and
+// applies its options goes through it, so a new kind is named here (and gets a constructor and a fill in fft_gpu_plan_info_hip).
+template <typename T>
+struct PlanSet {
+    ffteng::Pow2Plan<T, HipRT>* pow2 = nullptr;
+    ffteng::BluesteinPlan<T, HipRT>* blue = nullptr;
+    ffteng::MixedRadixPlan<T, HipRT>* mixed = nullptr;
+    // plans built on the batched engine (fft_plans_ext.h)
+    ffteng::Plan2D<T, HipRT>* two_d = nullptr;
+    ffteng::RealPlan<T, HipRT>* real = nullptr;
+    ffteng::FusedPlan<T, HipRT>* fused = nullptr;
+    ffteng::FramesPlan<T, HipRT>* frames = nullptr;         // STFT / spectrogram / Welch on overlapping frames
+    ffteng::IFramesPlan<T, HipRT>* iframes = nullptr;       // inverse STFT: one-sided rows -> real signals by overlap-add
+    ffteng::CrossFramesPlan<T, HipRT>* cross = nullptr;     // cross-spectral density / coherence / transfer estimate on the frames of signal pairs
+    ffteng::FilterPlan<T, HipRT>* filter = nullptr;         // overlap-save FIR filtering of long signals
+    ffteng::Conv2DPlan<T, HipRT>* conv2d = nullptr;         // 2D convolution / spectrum filtering of images
+    ffteng::Real2DPlan<T, HipRT>* real2d = nullptr;         // rfft2 / irfft2 of real images
+    template <class F>
+    void each(F&& f) {
+        f(pow2); f(blue); f(mixed); f(two_d); f(real); f(fused); f(frames); f(iframes); f(cross); f(filter); f(conv2d); f(real2d);
+    }
+    // a caller's untyped array as complex / real values of this precision
+    static const fftk::cpx<T>* c(const void* v) { return (const fftk::cpx<T>*)v; }
+    static fftk::cpx<T>* c(void* v) { return (fftk::cpx<T>*)v; }
+    static const T* r(const void* v) { return (const T*)v; }
+    static T* r(void* v) { return (T*)v; }
+};
+
 struct fft_gpu_plan {
     int n = 0, batch = 0, dir = -1, prec = 0, algo = 0, device = 0;
     bool pow2 = true;
     HipRT rt;
     hipStream_t own_stream = nullptr;
-    ffteng::Pow2Plan<float, HipRT>* p32 = nullptr;
-    ffteng::Pow2Plan<double, HipRT>* p64 = nullptr;
-    ffteng::BluesteinPlan<float, HipRT>* b32 = nullptr;
-    ffteng::BluesteinPlan<double, HipRT>* b64 = nullptr;
-    ffteng::MixedRadixPlan<float, HipRT>* m32 = nullptr;
-    ffteng::MixedRadixPlan<double, HipRT>* m64 = nullptr;
-    // plans built on the batched engine (fft_plans_ext.h); kind says which member is live
-    int kind = 0;  // 0 complex 1D, 1 complex 2D (n = rows * cols, batch = matrices), 2 r2c, 3 c2r, 4 fused consumer, 5 frames, 6 inverse frames, 7 cross frames, 8 FIR filter, 9 2D convolution, 10 real 2D forward, 11 real 2D inverse
+    // the PLAN_* below: which execute entry point the plan answers to.  PLAN_C2C: the power-of-two, Bluestein or mixed-radix plan of a
+    // complex 1D transform; PLAN_2D: n = rows * cols, batch = matrices; PLAN_R2C / PLAN_C2R: both a RealPlan
+    int kind = 0;
     int rows = 0, cols = 0;
-    ffteng::Plan2D<float, HipRT>* d32 = nullptr;
-    ffteng::Plan2D<double, HipRT>* d64 = nullptr;
-    ffteng::RealPlan<float, HipRT>* r32 = nullptr;
-    ffteng::RealPlan<double, HipRT>* r64 = nullptr;
-    ffteng::FusedPlan<float, HipRT>* f32 = nullptr;
-    ffteng::FusedPlan<double, HipRT>* f64 = nullptr;
-    ffteng::FramesPlan<float, HipRT>* w32 = nullptr;  // STFT / spectrogram / Welch on overlapping frames
-    ffteng::FramesPlan<double, HipRT>* w64 = nullptr;
-    ffteng::IFramesPlan<float, HipRT>* i32 = nullptr;  // inverse STFT: one-sided rows -> real signals by overlap-add
-    ffteng::IFramesPlan<double, HipRT>* i64 = nullptr;
-    ffteng::CrossFramesPlan<float, HipRT>* x32 = nullptr;  // cross-spectral density / coherence / transfer estimate on the frames of signal pairs
-    ffteng::CrossFramesPlan<double, HipRT>* x64 = nullptr;
-    ffteng::FilterPlan<float, HipRT>* s32 = nullptr;  // overlap-save FIR filtering of long signals
-    ffteng::FilterPlan<double, HipRT>* s64 = nullptr;
-    ffteng::Conv2DPlan<float, HipRT>* c32 = nullptr;  // 2D convolution / spectrum filtering of images
-    ffteng::Conv2DPlan<double, HipRT>* c64 = nullptr;
-    ffteng::Real2DPlan<float, HipRT>* q32 = nullptr;  // rfft2 / irfft2 of real images
-    ffteng::Real2DPlan<double, HipRT>* q64 = nullptr;
+    PlanSet<float> set32;
+    PlanSet<double> set64;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11 };
@@ -411,53 +420,27 @@ int team_status_of(Core* core) {
     return (int)st;
 }
 
+// f(set) on the set of the handle's precision
+template <class F>
+auto with_set(fft_gpu_plan* p, F&& f) {
+    return p->prec == FFT_PREC_F32 ? f(p->set32) : f(p->set64);
+}
+
+// f(plan) on the handle's live plan object, whatever its kind
+template <class F>
+void for_live_plan(fft_gpu_plan* p, F&& f) {
+    with_set(p, [&](auto& s) {
+        s.each([&](auto* q) {
+            if (q) f(q);
+        });
+    });
+}
+
 // every power-of-two core of a plan, whatever it is built of (Bluestein, 2D, real and fused plans run their transforms on cores of
-// their own: a team kernel's timeout there must reach fft_gpu_plan_sync like any other)
+// their own: a team kernel's timeout there must reach fft_gpu_plan_sync like any other).  Each plan class lists its own (each_core)
 template <class F>
 void for_each_core(fft_gpu_plan* p, F&& f) {
-    auto any = [&](auto* a) {
-        if (!a) return;
-        if (a->p2) f(a->p2);
-        if (a->bl) f(&a->bl->core);
-    };
-    if (p->p32) f(p->p32);
-    if (p->p64) f(p->p64);
-    if (p->b32) f(&p->b32->core);
-    if (p->b64) f(&p->b64->core);
-    auto two = [&](auto* d) {
-        if (!d) return;
-        any(&d->rowp);
-        if (d->colp) f(d->colp);
-        any(d->colt);
-    };
-    two(p->d32); two(p->d64);
-    if (p->r32) any(&p->r32->core);
-    if (p->r64) any(&p->r64->core);
-    if (p->f32) f(&p->f32->core);
-    if (p->f64) f(&p->f64->core);
-    if (p->w32) f(&p->w32->core);
-    if (p->w64) f(&p->w64->core);
-    if (p->i32) f(&p->i32->core);
-    if (p->i64) f(&p->i64->core);
-    if (p->x32) f(&p->x32->inner.core);
-    if (p->x64) f(&p->x64->inner.core);
-    if (p->s32) f(&p->s32->core);
-    if (p->s64) f(&p->s64->core);
-    auto conv = [&](auto* c) {
-        if (!c) return;
-        f(&c->rowp);
-        if (c->round.colp.ok) f(&c->round.colp);
-        two(c->fwd); two(c->inv);
-    };
-    conv(p->c32); conv(p->c64);
-    auto real2d = [&](auto* q) {
-        if (!q) return;
-        if (q->core.ok) f(&q->core);
-        if (q->cstep.colp.ok) f(&q->cstep.colp);
-        if (q->rp) any(&q->rp->core);
-        any(q->colt);
-    };
-    real2d(p->q32); real2d(p->q64);
+    for_live_plan(p, [&](auto* q) { q->each_core(f); });
 }
 
 // the worst of the plan's cores: TIMEOUT (2) > NO_TEAMS (1) > OK (0) > no team kernel / nothing launched (-1)
@@ -483,46 +466,11 @@ void plan_io_bytes(const fft_gpu_plan* p, size_t* in_bytes, size_t* out_bytes) {
     }
 }
 
-// nb > 0: only the first nb transforms of the plan's batch (1D complex plans; the host-pointer pipeline's last group)
-int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
-    if (!p || !d_in || !d_out || nb > p->batch) return -1;
+// The common end of every execute: on the plan's device, call(set) launches and answers 0 / -1; then the launch error, if any
+template <class F>
+int run_on_device(fft_gpu_plan* p, F&& call) {
     DeviceGuard guard(p->device);
-    const bool inv = p->dir > 0;
-    if (nb > 0 && nb < p->batch) {
-        if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, nb, inv);
-        else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb, inv);
-        else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, nb);
-        else if (p->b64) p->b64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb);
-        else if (p->m32) p->m32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, nb, inv);
-        else if (p->m64) p->m64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, nb, inv);
-        else return -1;
-        hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) {
-            fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e2));
-            return -1;
-        }
-        return 0;
-    }
-    if (p->d32) p->d32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
-    else if (p->d64) p->d64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch);
-    else if (p->r32 && p->kind == PLAN_R2C) p->r32->execute_r2c((const float*)d_in, (fftk::cpx<float>*)d_out, p->batch);
-    else if (p->r64 && p->kind == PLAN_R2C) p->r64->execute_r2c((const double*)d_in, (fftk::cpx<double>*)d_out, p->batch);
-    else if (p->r32) p->r32->execute_c2r((const fftk::cpx<float>*)d_in, (float*)d_out, p->batch);
-    else if (p->r64) p->r64->execute_c2r((const fftk::cpx<double>*)d_in, (double*)d_out, p->batch);
-    else if (p->f32 || p->f64) return -1;  // fused consumers take two inputs: fft_gpu_execute_fused_hip
-    else if (p->w32 || p->w64) return -1;  // frames plans take a signal pitch and a sample rate: fft_gpu_execute_frames_hip
-    else if (p->i32 || p->i64) return -1;  // inverse frames plans take a signal pitch: fft_gpu_execute_iframes_hip
-    else if (p->x32 || p->x64) return -1;  // cross frames plans take two signals: fft_gpu_execute_cross_frames_hip
-    else if (p->s32 || p->s64) return -1;  // filter plans take two pitches: fft_gpu_execute_filter_hip
-    else if (p->c32 || p->c64) return -1;  // 2D convolution plans take two pitches: fft_gpu_execute_conv2d_hip
-    else if (p->q32 || p->q64) return -1;  // real 2D plans take two pitches: fft_gpu_execute_real2d_hip
-    else if (p->p32) p->p32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
-    else if (p->p64) p->p64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
-    else if (p->b32) p->b32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch);
-    else if (p->b64) p->b64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch);
-    else if (p->m32) p->m32->execute((const fftk::cpx<float>*)d_in, (fftk::cpx<float>*)d_out, p->batch, inv);
-    else if (p->m64) p->m64->execute((const fftk::cpx<double>*)d_in, (fftk::cpx<double>*)d_out, p->batch, inv);
-    else return -1;
+    if (with_set(p, call) != 0) return -1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
@@ -530,6 +478,86 @@ int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     }
     return 0;
 }
+
+// nb in (0, batch): only the first nb transforms of the plan's batch (1D complex plans; the host-pointer pipeline's last group).  The
+// kinds from PLAN_FUSED on take arguments of their own (a second input, pitches, a sample rate) through their own entry points
+int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
+    if (!p || !d_in || !d_out || nb > p->batch) return -1;
+    const bool part = nb > 0 && nb < p->batch;
+    if (part ? p->kind != PLAN_C2C : p->kind >= PLAN_FUSED) return -1;
+    if (!part) nb = p->batch;
+    const bool inv = p->dir > 0;
+    return run_on_device(p, [&](auto& s) {
+        if (p->kind == PLAN_2D) s.two_d->execute(s.c(d_in), s.c(d_out), nb);
+        else if (p->kind == PLAN_R2C) s.real->execute_r2c(s.r(d_in), s.c(d_out), nb);
+        else if (p->kind == PLAN_C2R) s.real->execute_c2r(s.c(d_in), s.r(d_out), nb);
+        else if (s.pow2) s.pow2->execute(s.c(d_in), s.c(d_out), nb, inv);
+        else if (s.blue) s.blue->execute(s.c(d_in), s.c(d_out), nb);
+        else if (s.mixed) s.mixed->execute(s.c(d_in), s.c(d_out), nb, inv);
+        else return -1;
+        return 0;
+    });
+}
+
+// ---- every plan constructor: the shell (handle, device, stream, runtime policy), one member of the set, the common end
+fft_gpu_plan* new_plan_shell(int n, int batch, int dir, fft_precision_t prec, int kind) {
+    if (!g_initialized) {
+        fprintf(stderr, "fft_hip: plan requested before fft_gpu_init\n");
+        return NULL;
+    }
+    if (prec != FFT_PREC_F32 && prec != FFT_PREC_F64) return NULL;
+    fft_gpu_plan* p = new (std::nothrow) fft_gpu_plan();
+    if (!p) return NULL;
+    p->n = n; p->batch = batch; p->dir = dir < 0 ? -1 : 1; p->prec = (int)prec; p->kind = kind; p->pow2 = false;
+    int dev = g_device;
+    (void)hipGetDevice(&dev);
+    p->device = dev;
+    const DeviceInfo* di = device_info(dev);
+    if (!di || hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) {
+        (void)hipGetLastError();
+        delete p;
+        return NULL;
+    }
+    __atomic_fetch_add(&g_count_streams, 1ll, __ATOMIC_RELAXED);  // (fft_gpu_debug_counters_hip: every stream the backend creates)
+    p->rt.stream = p->own_stream;
+    p->rt.lds_limit = di->lds_limit;
+    p->rt.cus = di->cus;
+    p->rt.gfx950 = di->gfx950;
+    p->rt.policy = g_policy;
+    return p;
+}
+// member = a new plan object, built on the handle's runtime with the arguments its build() takes after that
+template <class P, class... A>
+bool construct(fft_gpu_plan* p, P*& member, A... args) {
+    member = new (std::nothrow) P();
+    return member && member->build(&p->rt, args...);
+}
+// build(set) constructs the handle's plan in the set of its precision; then the end every plan of the batched engine shares
+template <class B>
+fft_gpu_plan_t make_plan(fft_gpu_plan* p, const char* what, B&& build) {
+    bool ok = with_set(p, build);
+    if (ok) for_each_core(p, [](auto* c) { c->team_replay = false; });  // composite plans: a team timeout in a core is reported, never replayed
+    if (ok) ok = (hipStreamSynchronize(p->own_stream) == hipSuccess);
+    if (!ok) {
+        fprintf(stderr, "fft_hip: could not build a %s plan\n", what);
+        (void)hipGetLastError();
+        fft_gpu_destroy_plan_hip(p);
+        return NULL;
+    }
+    return p;
+}
+
+// does a plan class take FFT_GPU_OPT_NO_FUSION / FFT_GPU_OPT_NO_CHAIN?  It says so itself, by having the setter
+template <class P, class = void> struct takes_no_fusion : std::false_type {};
+template <class P> struct takes_no_fusion<P, std::void_t<decltype(std::declval<P&>().set_no_fusion(true))>> : std::true_type {};
+template <class P, class = void> struct takes_no_chain : std::false_type {};
+template <class P> struct takes_no_chain<P, std::void_t<decltype(std::declval<P&>().set_no_chain(0))>> : std::true_type {};
+
+// the getters of one plan kind: -1 on a handle of any other kind
+#define FFT_PLAN_GETTER(name, member, expr)                                                                          \
+    int name(fft_gpu_plan_t p) {                                                                                     \
+        return !p ? -1 : with_set(p, [](auto& s) { auto* q = s.member; return q ? (int)(expr) : -1; });               \
+    }
 
 }  // namespace
 
@@ -677,73 +705,29 @@ fft_gpu_plan_t fft_gpu_plan_1d_ex_hip(int n, int batch, fft_direction dir, fft_p
         fprintf(stderr, "fft_hip: invalid plan arguments (n=%d batch=%d prec=%d algo=%d)\n", n, batch, (int)prec, (int)algo);
         return NULL;
     }
-    fft_gpu_plan* p = new (std::nothrow) fft_gpu_plan();
+    fft_gpu_plan* p = new_plan_shell(n, batch, (int)dir, prec, PLAN_C2C);
     if (!p) return NULL;
-    p->n = n;
-    p->batch = batch;
-    p->dir = ((int)dir < 0) ? -1 : 1;
-    p->prec = (int)prec;
     p->algo = (int)algo;
     p->pow2 = (n & (n - 1)) == 0 && algo != FFT_GPU_ALGO_BLUESTEIN;
     if (algo == FFT_GPU_ALGO_BLUESTEIN) algo = FFT_GPU_ALGO_AUTO;
     // 7-smooth lengths: the mixed-radix plan when asked for by name, or by AUTO under the smooth policy; a power of two keeps
     // the plan AUTO builds, any other length falls back to chirp-z
-    bool mixed = !p->pow2 && (algo == FFT_GPU_ALGO_MIXED_RADIX || (algo == FFT_GPU_ALGO_AUTO && p->algo == FFT_GPU_ALGO_AUTO && g_smooth_policy == 1)) &&
-                 ffteng::mr_passes(n) > 0;
+    const bool mixed = !p->pow2 && (algo == FFT_GPU_ALGO_MIXED_RADIX || (algo == FFT_GPU_ALGO_AUTO && p->algo == FFT_GPU_ALGO_AUTO && g_smooth_policy == 1)) &&
+                       ffteng::mr_passes(n) > 0;
     if (algo == FFT_GPU_ALGO_MIXED_RADIX) algo = FFT_GPU_ALGO_AUTO;
-    int dev = g_device;
-    (void)hipGetDevice(&dev);
-    p->device = dev;
-    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        delete p;
-        return NULL;
-    }
-    __atomic_fetch_add(&g_count_streams, 1ll, __ATOMIC_RELAXED);  // (fft_gpu_debug_counters_hip: every stream the backend creates)
-    const DeviceInfo* di = device_info(dev);
-    if (!di) {
-        fft_gpu_destroy_plan_hip(p);
-        return NULL;
-    }
-    p->rt.stream = p->own_stream;
-    p->rt.lds_limit = di->lds_limit;
-    p->rt.cus = di->cus;
-    p->rt.gfx950 = di->gfx950;
-    p->rt.policy = g_policy;
-    bool ok = false;
-    const int log2n = ffteng::ilog2(n);
-    if (p->pow2) {
-        if (prec == FFT_PREC_F32) {
-            p->p32 = new (std::nothrow) ffteng::Pow2Plan<float, HipRT>();
-            ok = p->p32 && p->p32->build(&p->rt, log2n, (int)algo, batch);
-        } else {
-            p->p64 = new (std::nothrow) ffteng::Pow2Plan<double, HipRT>();
-            ok = p->p64 && p->p64->build(&p->rt, log2n, (int)algo, batch);
+    bool ok = with_set(p, [&](auto& s) {
+        if (p->pow2) return construct(p, s.pow2, ffteng::ilog2(n), (int)algo, batch);
+        if (mixed) {
+            if (construct(p, s.mixed, n, batch)) return true;
+            delete s.mixed;  // (a device whose LDS holds no such schedule: chirp-z)
+            s.mixed = nullptr;
         }
-    }
-    if (!p->pow2 && mixed) {
-        if (prec == FFT_PREC_F32) {
-            p->m32 = new (std::nothrow) ffteng::MixedRadixPlan<float, HipRT>();
-            ok = p->m32 && p->m32->build(&p->rt, n, batch);
-            if (!ok) { delete p->m32; p->m32 = nullptr; }
-        } else {
-            p->m64 = new (std::nothrow) ffteng::MixedRadixPlan<double, HipRT>();
-            ok = p->m64 && p->m64->build(&p->rt, n, batch);
-            if (!ok) { delete p->m64; p->m64 = nullptr; }
-        }
-        mixed = ok;  // (a device whose LDS holds no such schedule: chirp-z)
-    }
-    if (!p->pow2 && !mixed) {
         if (n > (1 << 29)) {
             fprintf(stderr, "fft_hip: Bluestein length %d too large\n", n);
-        } else if (prec == FFT_PREC_F32) {
-            p->b32 = new (std::nothrow) ffteng::BluesteinPlan<float, HipRT>();
-            ok = p->b32 && p->b32->build(&p->rt, n, p->dir, (int)algo, batch);
-        } else {
-            p->b64 = new (std::nothrow) ffteng::BluesteinPlan<double, HipRT>();
-            ok = p->b64 && p->b64->build(&p->rt, n, p->dir, (int)algo, batch);
+            return false;
         }
-    }
+        return construct(p, s.blue, n, p->dir, (int)algo, batch);
+    });
     if (ok && !p->pow2) for_each_core(p, [](auto* c) { c->team_replay = false; });  // (a core of a composite plan transforms the plan's own intermediates)
     if (ok) ok = (hipStreamSynchronize(p->own_stream) == hipSuccess);
     if (!ok) {
@@ -764,74 +748,14 @@ void fft_gpu_destroy_plan_hip(fft_gpu_plan_t p) {
     {
         DeviceGuard guard(p->device);
         if (p->rt.stream) (void)hipStreamSynchronize(p->rt.stream);
-        delete p->p32;
-        delete p->p64;
-        delete p->b32;
-        delete p->b64;
-        delete p->m32;
-        delete p->m64;
-        delete p->d32;
-        delete p->d64;
-        delete p->r32;
-        delete p->r64;
-        delete p->f32;
-        delete p->f64;
-        delete p->w32;
-        delete p->w64;
-        delete p->i32;
-        delete p->i64;
-        delete p->x32;
-        delete p->x64;
-        delete p->s32;
-        delete p->s64;
-        delete p->c32;
-        delete p->c64;
-        delete p->q32;
-        delete p->q64;
+        auto drop = [](auto*& q) { delete q; q = nullptr; };
+        p->set32.each(drop);
+        p->set64.each(drop);
         if (p->ev0) (void)hipEventDestroy(p->ev0);
         if (p->ev1) (void)hipEventDestroy(p->ev1);
         if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     }
     delete p;
-}
-
-// ---- plans built on the batched engine (fft_plans_ext.h): common shell
-static fft_gpu_plan* new_plan_shell(int n, int batch, int dir, fft_precision_t prec, int kind) {
-    if (!g_initialized) {
-        fprintf(stderr, "fft_hip: plan requested before fft_gpu_init\n");
-        return NULL;
-    }
-    if (prec != FFT_PREC_F32 && prec != FFT_PREC_F64) return NULL;
-    fft_gpu_plan* p = new (std::nothrow) fft_gpu_plan();
-    if (!p) return NULL;
-    p->n = n; p->batch = batch; p->dir = dir < 0 ? -1 : 1; p->prec = (int)prec; p->kind = kind; p->pow2 = false;
-    int dev = g_device;
-    (void)hipGetDevice(&dev);
-    p->device = dev;
-    const DeviceInfo* di = device_info(dev);
-    if (!di || hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        delete p;
-        return NULL;
-    }
-    __atomic_fetch_add(&g_count_streams, 1ll, __ATOMIC_RELAXED);
-    p->rt.stream = p->own_stream;
-    p->rt.lds_limit = di->lds_limit;
-    p->rt.cus = di->cus;
-    p->rt.gfx950 = di->gfx950;
-    p->rt.policy = g_policy;
-    return p;
-}
-static fft_gpu_plan_t finish_plan(fft_gpu_plan* p, bool ok, const char* what) {
-    if (ok) for_each_core(p, [](auto* c) { c->team_replay = false; });  // composite plans: a team timeout in a core is reported, never replayed
-    if (ok) ok = (hipStreamSynchronize(p->own_stream) == hipSuccess);
-    if (!ok) {
-        fprintf(stderr, "fft_hip: could not build a %s plan\n", what);
-        (void)hipGetLastError();
-        fft_gpu_destroy_plan_hip(p);
-        return NULL;
-    }
-    return p;
 }
 
 // FFT_GPU_ALGO_AUTO / FFT_GPU_ALGO_MIXED_RADIX of the 2D and real plans: does the plan put its 7-smooth lengths on the
@@ -852,15 +776,7 @@ fft_gpu_plan_t fft_gpu_plan_2d_algo_hip(int rows, int cols, int n_matrices, fft_
     fft_gpu_plan* p = new_plan_shell(rows * cols, n_matrices, (int)dir, prec, PLAN_2D);
     if (!p) return NULL;
     p->rows = rows; p->cols = cols;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->d32 = new (std::nothrow) ffteng::Plan2D<float, HipRT>();
-        ok = p->d32 && p->d32->build(&p->rt, rows, cols, p->dir, n_matrices, smooth == 1);
-    } else {
-        p->d64 = new (std::nothrow) ffteng::Plan2D<double, HipRT>();
-        ok = p->d64 && p->d64->build(&p->rt, rows, cols, p->dir, n_matrices, smooth == 1);
-    }
-    return finish_plan(p, ok, "2D");
+    return make_plan(p, "2D", [&](auto& s) { return construct(p, s.two_d, rows, cols, p->dir, n_matrices, smooth == 1); });
 }
 fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec) {
     return fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, dir, prec, FFT_GPU_ALGO_AUTO);
@@ -876,15 +792,7 @@ static fft_gpu_plan_t plan_real(int n, int batch, fft_precision_t prec, bool r2c
     }
     fft_gpu_plan* p = new_plan_shell(n, batch, r2c ? -1 : 1, prec, r2c ? PLAN_R2C : PLAN_C2R);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->r32 = new (std::nothrow) ffteng::RealPlan<float, HipRT>();
-        ok = p->r32 && p->r32->build(&p->rt, n, r2c, batch, smooth == 1);
-    } else {
-        p->r64 = new (std::nothrow) ffteng::RealPlan<double, HipRT>();
-        ok = p->r64 && p->r64->build(&p->rt, n, r2c, batch, smooth == 1);
-    }
-    return finish_plan(p, ok, r2c ? "r2c" : "c2r");
+    return make_plan(p, r2c ? "r2c" : "c2r", [&](auto& s) { return construct(p, s.real, n, r2c, batch, smooth == 1); });
 }
 fft_gpu_plan_t fft_gpu_plan_r2c_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo) { return plan_real(n, batch, prec, true, algo); }
 fft_gpu_plan_t fft_gpu_plan_c2r_1d_algo_hip(int n, int batch, fft_precision_t prec, fft_gpu_algo_t algo) { return plan_real(n, batch, prec, false, algo); }
@@ -900,40 +808,18 @@ fft_gpu_plan_t fft_gpu_plan_fused_hip(fft_gpu_fused_t kind, int nx, int nh, cons
     }
     fft_gpu_plan* p = new_plan_shell(nx, batch, -1, prec, PLAN_FUSED);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->f32 = new (std::nothrow) ffteng::FusedPlan<float, HipRT>();
-        ok = p->f32 && p->f32->build(&p->rt, (int)kind, nx, nh, (const fftk::cpx<float>*)h_host, batch);
-    } else {
-        p->f64 = new (std::nothrow) ffteng::FusedPlan<double, HipRT>();
-        ok = p->f64 && p->f64->build(&p->rt, (int)kind, nx, nh, (const fftk::cpx<double>*)h_host, batch);
-    }
-    return finish_plan(p, ok, "fused");
+    return make_plan(p, "fused", [&](auto& s) { return construct(p, s.fused, (int)kind, nx, nh, s.c(h_host), batch); });
 }
 // elements per output row of a fused plan (complex values; FFT_GPU_FUSED_PSD: real values)
-int fft_gpu_fused_out_len_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->f32) return p->f32->out_len();
-    if (p->f64) return p->f64->out_len();
-    return -1;
-}
+FFT_PLAN_GETTER(fft_gpu_fused_out_len_hip, fused, q->out_len())
 // async on the plan's stream.  d_x: [batch][nx]; d_y: second signal (XCORR) or NULL; d_out: [batch][out_len]
 int fft_gpu_execute_fused_hip(fft_gpu_plan_t p, const void* d_x, const void* d_y, void* d_out, double sample_rate) {
-    if (!p || !d_x || !d_out || (!p->f32 && !p->f64)) return -1;
-    DeviceGuard guard(p->device);
-    if (p->f32) {
-        if (p->f32->kind == ffteng::FUSED_XCORR && !d_y) return -1;
-        p->f32->execute((const fftk::cpx<float>*)d_x, (const fftk::cpx<float>*)d_y, d_out, p->batch, (float)sample_rate);
-    } else {
-        if (p->f64->kind == ffteng::FUSED_XCORR && !d_y) return -1;
-        p->f64->execute((const fftk::cpx<double>*)d_x, (const fftk::cpx<double>*)d_y, d_out, p->batch, sample_rate);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_x || !d_out || p->kind != PLAN_FUSED) return -1;
+    return run_on_device(p, [&](auto& s) {
+        if (s.fused->kind == ffteng::FUSED_XCORR && !d_y) return -1;
+        s.fused->execute(s.c(d_x), s.c(d_y), d_out, p->batch, sample_rate);  // (rounded to the plan's precision)
+        return 0;
+    });
 }
 
 // STFT / spectrogram / Welch PSD on overlapping frames (fft_plans_ext.h FramesPlan); w_host: the n window values of
@@ -950,15 +836,9 @@ static fft_gpu_plan_t plan_frames(int n, int hop, int signal_len, int n_signals,
     const int nw = (signal_len - (n - hop)) / hop;
     fft_gpu_plan* p = new_plan_shell(n, n_signals * nw, -1, prec, PLAN_FRAMES);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->w32 = new (std::nothrow) ffteng::FramesPlan<float, HipRT>();
-        ok = p->w32 && p->w32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out, real_input);
-    } else {
-        p->w64 = new (std::nothrow) ffteng::FramesPlan<double, HipRT>();
-        ok = p->w64 && p->w64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out, real_input);
-    }
-    return finish_plan(p, ok, real_input ? "real frames" : "frames");
+    return make_plan(p, real_input ? "real frames" : "frames", [&](auto& s) {
+        return construct(p, s.frames, n, hop, signal_len, n_signals, (int)window, s.r(w_host), (int)out, real_input);
+    });
 }
 fft_gpu_plan_t fft_gpu_plan_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
                                        fft_gpu_frames_out_t out, fft_precision_t prec) {
@@ -970,27 +850,13 @@ fft_gpu_plan_t fft_gpu_plan_frames_real_hip(int n, int hop, int signal_len, int 
 }
 // frames per signal: nw = (signal_len - (n - hop)) / hop
 int fft_gpu_frames_count_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->w32) return p->w32->nw;
-    if (p->w64) return p->w64->nw;
-    if (p->x32) return p->x32->inner.nw;
-    if (p->x64) return p->x64->inner.nw;
-    return -1;
+    return !p ? -1 : with_set(p, [](auto& s) { return s.frames ? s.frames->nw : s.cross ? s.cross->inner.nw : -1; });
 }
 // async on the plan's stream.  d_x: the signals, signal_pitch elements apart (0: signal_len; reals for a real frames plan, which
 // reads d_x as such); d_out: see fft_gpu_frames_out_t
 int fft_gpu_execute_frames_hip(fft_gpu_plan_t p, const void* d_x, long long signal_pitch, void* d_out, double sample_rate) {
-    if (!p || !d_x || !d_out || d_x == d_out || (!p->w32 && !p->w64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->w32 ? p->w32->execute((const fftk::cpx<float>*)d_x, signal_pitch, d_out, sample_rate)
-                          : p->w64->execute((const fftk::cpx<double>*)d_x, signal_pitch, d_out, sample_rate);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_x || !d_out || d_x == d_out || p->kind != PLAN_FRAMES) return -1;
+    return run_on_device(p, [&](auto& s) { return s.frames->execute(s.c(d_x), signal_pitch, d_out, sample_rate); });
 }
 
 // Inverse STFT by weighted overlap-add (fft_plans_ext.h IFramesPlan); w_host: the n window values of FFT_GPU_WINDOW_USER (host
@@ -1005,41 +871,14 @@ fft_gpu_plan_t fft_gpu_plan_iframes_real_hip(int n, int hop, int n_frames, int n
     }
     fft_gpu_plan* p = new_plan_shell(n, n_signals * n_frames, 1, prec, PLAN_IFRAMES);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->i32 = new (std::nothrow) ffteng::IFramesPlan<float, HipRT>();
-        ok = p->i32 && p->i32->build(&p->rt, n, hop, n_frames, n_signals, (int)window, (const float*)w_host);
-    } else {
-        p->i64 = new (std::nothrow) ffteng::IFramesPlan<double, HipRT>();
-        ok = p->i64 && p->i64->build(&p->rt, n, hop, n_frames, n_signals, (int)window, (const double*)w_host);
-    }
-    return finish_plan(p, ok, "inverse frames");
+    return make_plan(p, "inverse frames", [&](auto& s) { return construct(p, s.iframes, n, hop, n_frames, n_signals, (int)window, s.r(w_host)); });
 }
-int fft_gpu_iframes_len_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->i32) return (int)p->i32->out_len();
-    if (p->i64) return (int)p->i64->out_len();
-    return -1;
-}
-int fft_gpu_iframes_unrecoverable_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->i32) return p->i32->unrecoverable;
-    if (p->i64) return p->i64->unrecoverable;
-    return -1;
-}
+FFT_PLAN_GETTER(fft_gpu_iframes_len_hip, iframes, q->out_len())
+FFT_PLAN_GETTER(fft_gpu_iframes_unrecoverable_hip, iframes, q->unrecoverable)
 // async on the plan's stream.  d_X: [signals][frames][n/2 + 1] complex; d_y: the real signals, signal_pitch reals apart (0: out_len)
 int fft_gpu_execute_iframes_hip(fft_gpu_plan_t p, const void* d_X, void* d_y, long long signal_pitch) {
-    if (!p || !d_X || !d_y || d_X == d_y || (!p->i32 && !p->i64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->i32 ? p->i32->execute((const fftk::cpx<float>*)d_X, (float*)d_y, signal_pitch)
-                          : p->i64->execute((const fftk::cpx<double>*)d_X, (double*)d_y, signal_pitch);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_X || !d_y || d_X == d_y || p->kind != PLAN_IFRAMES) return -1;
+    return run_on_device(p, [&](auto& s) { return s.iframes->execute(s.c(d_X), s.r(d_y), signal_pitch); });
 }
 
 // Cross-spectral density, coherence and H1 transfer estimate of signal pairs on overlapping frames (fft_plans_ext.h CrossFramesPlan);
@@ -1056,15 +895,9 @@ static fft_gpu_plan_t plan_cross(int n, int hop, int signal_len, int n_signals, 
     const int nw = (signal_len - (n - hop)) / hop;
     fft_gpu_plan* p = new_plan_shell(n, n_signals * nw, -1, prec, PLAN_CROSS);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->x32 = new (std::nothrow) ffteng::CrossFramesPlan<float, HipRT>();
-        ok = p->x32 && p->x32->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const float*)w_host, (int)out, real_input);
-    } else {
-        p->x64 = new (std::nothrow) ffteng::CrossFramesPlan<double, HipRT>();
-        ok = p->x64 && p->x64->build(&p->rt, n, hop, signal_len, n_signals, (int)window, (const double*)w_host, (int)out, real_input);
-    }
-    return finish_plan(p, ok, real_input ? "real cross frames" : "cross frames");
+    return make_plan(p, real_input ? "real cross frames" : "cross frames", [&](auto& s) {
+        return construct(p, s.cross, n, hop, signal_len, n_signals, (int)window, s.r(w_host), (int)out, real_input);
+    });
 }
 fft_gpu_plan_t fft_gpu_plan_cross_frames_hip(int n, int hop, int signal_len, int n_signals, fft_gpu_window_t window, const void* w_host,
                                              fft_gpu_cross_out_t out, fft_precision_t prec) {
@@ -1075,26 +908,13 @@ fft_gpu_plan_t fft_gpu_plan_cross_frames_real_hip(int n, int hop, int signal_len
     return plan_cross(n, hop, signal_len, n_signals, window, w_host, out, prec, true);
 }
 // frames per chunk of the reduction (a function of nw, n_signals and n alone); -1: not a cross frames plan
-int fft_gpu_cross_chunk_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->x32) return p->x32->C;
-    if (p->x64) return p->x64->C;
-    return -1;
-}
+FFT_PLAN_GETTER(fft_gpu_cross_chunk_hip, cross, q->C)
 // async on the plan's stream.  d_x, d_y: the signals of every pair, each side with its own pitch in elements (reals for a real plan;
 // 0: signal_len); d_x == d_y is legal; d_out (see fft_gpu_cross_out_t) must overlap neither
 int fft_gpu_execute_cross_frames_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, const void* d_y, long long y_pitch, void* d_out,
                                      double sample_rate) {
-    if (!p || !d_x || !d_y || !d_out || (!p->x32 && !p->x64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->x32 ? p->x32->execute(d_x, x_pitch, d_y, y_pitch, d_out, sample_rate) : p->x64->execute(d_x, x_pitch, d_y, y_pitch, d_out, sample_rate);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_x || !d_y || !d_out || p->kind != PLAN_CROSS) return -1;
+    return run_on_device(p, [&](auto& s) { return s.cross->execute(d_x, x_pitch, d_y, y_pitch, d_out, sample_rate); });
 }
 
 // Overlap-save FIR filtering (fft_plans_ext.h FilterPlan); h_host: n_taps complex taps of `prec` in host memory
@@ -1105,44 +925,20 @@ fft_gpu_plan_t fft_gpu_plan_filter_hip(int n_taps, const void* h_host, int signa
     }
     fft_gpu_plan* p = new_plan_shell(n, n_signals, -1, prec, PLAN_FILTER);
     if (!p) return NULL;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->s32 = new (std::nothrow) ffteng::FilterPlan<float, HipRT>();
-        ok = p->s32 && p->s32->build(&p->rt, n_taps, (const fftk::cpx<float>*)h_host, signal_len, n_signals, n, (int)out);
-        if (ok) { p->n = p->s32->n; p->batch = (int)p->s32->blocks(); }
-    } else {
-        p->s64 = new (std::nothrow) ffteng::FilterPlan<double, HipRT>();
-        ok = p->s64 && p->s64->build(&p->rt, n_taps, (const fftk::cpx<double>*)h_host, signal_len, n_signals, n, (int)out);
-        if (ok) { p->n = p->s64->n; p->batch = (int)p->s64->blocks(); }
-    }
-    return finish_plan(p, ok, "filter");
+    return make_plan(p, "filter", [&](auto& s) {
+        if (!construct(p, s.filter, n_taps, s.c(h_host), signal_len, n_signals, n, (int)out)) return false;
+        p->n = s.filter->n;  // the block length the plan chose, and its blocks
+        p->batch = (int)s.filter->blocks();
+        return true;
+    });
 }
-int fft_gpu_filter_out_len_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->s32) return p->s32->out_len;
-    if (p->s64) return p->s64->out_len;
-    return -1;
-}
-int fft_gpu_filter_block_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->s32) return p->s32->n;
-    if (p->s64) return p->s64->n;
-    return -1;
-}
+FFT_PLAN_GETTER(fft_gpu_filter_out_len_hip, filter, q->out_len)
+FFT_PLAN_GETTER(fft_gpu_filter_block_hip, filter, q->n)
 // async on the plan's stream.  d_x: the signals, x_pitch elements apart (0: signal_len); d_y: the outputs, y_pitch apart (0: out_len);
 // the two must not overlap
 int fft_gpu_execute_filter_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
-    if (!p || !d_x || !d_y || (!p->s32 && !p->s64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->s32 ? p->s32->execute((const fftk::cpx<float>*)d_x, x_pitch, (fftk::cpx<float>*)d_y, y_pitch)
-                          : p->s64->execute((const fftk::cpx<double>*)d_x, x_pitch, (fftk::cpx<double>*)d_y, y_pitch);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_x || !d_y || p->kind != PLAN_FILTER) return -1;
+    return run_on_device(p, [&](auto& s) { return s.filter->execute(s.c(d_x), x_pitch, s.c(d_y), y_pitch); });
 }
 
 // 2D convolution / spectrum filtering of row-major images (fft_plans_ext.h Conv2DPlan); k_host: krows x kcols complex of `prec` in host
@@ -1158,42 +954,17 @@ fft_gpu_plan_t fft_gpu_plan_conv2d_hip(int rows, int cols, int krows, int kcols,
     fft_gpu_plan* p = new_plan_shell(Q, n_matrices, -1, prec, PLAN_CONV2D);
     if (!p) return NULL;
     p->rows = rows; p->cols = cols;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->c32 = new (std::nothrow) ffteng::Conv2DPlan<float, HipRT>();
-        ok = p->c32 && p->c32->build(&p->rt, rows, cols, krows, kcols, (const fftk::cpx<float>*)k_host, n_matrices, (int)mode);
-    } else {
-        p->c64 = new (std::nothrow) ffteng::Conv2DPlan<double, HipRT>();
-        ok = p->c64 && p->c64->build(&p->rt, rows, cols, krows, kcols, (const fftk::cpx<double>*)k_host, n_matrices, (int)mode);
-    }
-    return finish_plan(p, ok, "2D convolution");
+    return make_plan(p, "2D convolution", [&](auto& s) { return construct(p, s.conv2d, rows, cols, krows, kcols, s.c(k_host), n_matrices, (int)mode); });
 }
-#define FFT_CONV2D_GETTER(name, field)      \
-    int name(fft_gpu_plan_t p) {            \
-        if (!p) return -1;                  \
-        if (p->c32) return p->c32->field;   \
-        if (p->c64) return p->c64->field;   \
-        return -1;                          \
-    }
-FFT_CONV2D_GETTER(fft_gpu_conv2d_out_rows_hip, out_rows)
-FFT_CONV2D_GETTER(fft_gpu_conv2d_out_cols_hip, out_cols)
-FFT_CONV2D_GETTER(fft_gpu_conv2d_padded_rows_hip, P)
-FFT_CONV2D_GETTER(fft_gpu_conv2d_padded_cols_hip, Q)
-#undef FFT_CONV2D_GETTER
+FFT_PLAN_GETTER(fft_gpu_conv2d_out_rows_hip, conv2d, q->out_rows)
+FFT_PLAN_GETTER(fft_gpu_conv2d_out_cols_hip, conv2d, q->out_cols)
+FFT_PLAN_GETTER(fft_gpu_conv2d_padded_rows_hip, conv2d, q->P)
+FFT_PLAN_GETTER(fft_gpu_conv2d_padded_cols_hip, conv2d, q->Q)
 // async on the plan's stream.  d_x: the images, x_pitch elements apart (0: rows * cols); d_y: the outputs, y_pitch apart (0: out_rows *
 // out_cols); the two must not overlap
 int fft_gpu_execute_conv2d_hip(fft_gpu_plan_t p, const void* d_x, long long x_pitch, void* d_y, long long y_pitch) {
-    if (!p || !d_x || !d_y || (!p->c32 && !p->c64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->c32 ? p->c32->execute((const fftk::cpx<float>*)d_x, x_pitch, (fftk::cpx<float>*)d_y, y_pitch)
-                          : p->c64->execute((const fftk::cpx<double>*)d_x, x_pitch, (fftk::cpx<double>*)d_y, y_pitch);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_x || !d_y || p->kind != PLAN_CONV2D) return -1;
+    return run_on_device(p, [&](auto& s) { return s.conv2d->execute(s.c(d_x), x_pitch, s.c(d_y), y_pitch); });
 }
 
 // real 2D transforms of row-major images, numpy's rfft2 / irfft2 (fft_plans_ext.h Real2DPlan)
@@ -1205,37 +976,16 @@ static fft_gpu_plan_t plan_real2d(int rows, int cols, int n_matrices, fft_precis
     fft_gpu_plan* p = new_plan_shell(cols, n_matrices, r2c ? -1 : 1, prec, r2c ? PLAN_R2C_2D : PLAN_C2R_2D);
     if (!p) return NULL;
     p->rows = rows; p->cols = cols;
-    bool ok;
-    if (prec == FFT_PREC_F32) {
-        p->q32 = new (std::nothrow) ffteng::Real2DPlan<float, HipRT>();
-        ok = p->q32 && p->q32->build(&p->rt, rows, cols, n_matrices, r2c);
-    } else {
-        p->q64 = new (std::nothrow) ffteng::Real2DPlan<double, HipRT>();
-        ok = p->q64 && p->q64->build(&p->rt, rows, cols, n_matrices, r2c);
-    }
-    return finish_plan(p, ok, r2c ? "real 2D forward" : "real 2D inverse");
+    return make_plan(p, r2c ? "real 2D forward" : "real 2D inverse", [&](auto& s) { return construct(p, s.real2d, rows, cols, n_matrices, r2c); });
 }
 fft_gpu_plan_t fft_gpu_plan_r2c_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec) { return plan_real2d(rows, cols, n_matrices, prec, true); }
 fft_gpu_plan_t fft_gpu_plan_c2r_2d_hip(int rows, int cols, int n_matrices, fft_precision_t prec) { return plan_real2d(rows, cols, n_matrices, prec, false); }
-int fft_gpu_real2d_bins_hip(fft_gpu_plan_t p) {
-    if (!p) return -1;
-    if (p->q32) return p->q32->hb;
-    if (p->q64) return p->q64->hb;
-    return -1;
-}
+FFT_PLAN_GETTER(fft_gpu_real2d_bins_hip, real2d, q->hb)
 // async on the plan's stream.  Forward: d_in the real images, d_out the one-sided spectra; inverse: the other way round.  Pitches in
 // elements of their own side between matrices (0: dense); the two buffers must not overlap
 int fft_gpu_execute_real2d_hip(fft_gpu_plan_t p, const void* d_in, long long in_pitch, void* d_out, long long out_pitch) {
-    if (!p || !d_in || !d_out || (!p->q32 && !p->q64)) return -1;
-    DeviceGuard guard(p->device);
-    const int rc = p->q32 ? p->q32->execute(d_in, in_pitch, d_out, out_pitch) : p->q64->execute(d_in, in_pitch, d_out, out_pitch);
-    if (rc != 0) return -1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        fprintf(stderr, "fft_hip: kernel launch failed: %s\n", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    if (!p || !d_in || !d_out || (p->kind != PLAN_R2C_2D && p->kind != PLAN_C2R_2D)) return -1;
+    return run_on_device(p, [&](auto& s) { return s.real2d->execute(d_in, in_pitch, d_out, out_pitch); });
 }
 
 int fft_gpu_plan_set_stream_hip(fft_gpu_plan_t p, void* hip_stream) {
@@ -1264,9 +1014,7 @@ int fft_gpu_plan_team_trace_hip(fft_gpu_plan_t p, void* d_trace, int events) {
         core->team.trace_events = d_trace ? events : 0;
         return 0;
     };
-    if (p->p32) return set(p->p32);
-    if (p->p64) return set(p->p64);
-    return -1;
+    return with_set(p, [&](auto& s) { return set(s.pow2); });
 }
 
 // Process-wide planner policy for plans created AFTER the call (a negative argument keeps the current value):
@@ -1448,19 +1196,17 @@ int fft_gpu_plan_measure_hip(fft_gpu_plan_t p, int iters) {
         if (team_wins) core->team.min_batch = 1;  // measured for this plan's batch: the static crossover no longer applies
         return team_wins ? 1 : 0;
     };
-    if (p->p32) return measure(p->p32);
-    if (p->p64) return measure(p->p64);
-    return 0;
+    return with_set(p, [&](auto& s) { return measure(s.pow2); });  // (plain power-of-two 1D plans; every other kind: 0)
 }
 
 int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, int value) {
     if (!p) return -1;
     auto each_core = [&](auto&& f) { for_each_core(p, f); };
+    int rc = -1;  // the options of the plan itself: 0 where the live plan's class takes them
     switch (option) {
         case FFT_GPU_OPT_TEAM_NO_REPLAY:
             // only plain 1D complex plans ever replay (the cores of composite plans transform the plan's own intermediates)
-            if (p->p32) p->p32->team_replay = value == 0;
-            if (p->p64) p->p64->team_replay = value == 0;
+            with_set(p, [&](auto& s) { if (s.pow2) s.pow2->team_replay = value == 0; });
             return 0;
         case FFT_GPU_OPT_TEAM_FORCE_FALLBACK:
             each_core([&](auto* c) { c->team_force_fallback = value != 0; });
@@ -1472,33 +1218,15 @@ int fft_gpu_plan_set_option_hip(fft_gpu_plan_t p, fft_gpu_plan_option_t option, 
             });
             return 0;
         case FFT_GPU_OPT_NO_FUSION:
-            if (p->b32) p->b32->no_fusion = value != 0;
-            if (p->b64) p->b64->no_fusion = value != 0;
-            if (p->f32) p->f32->no_fusion = value != 0;
-            if (p->f64) p->f64->no_fusion = value != 0;
-            if (p->w32) p->w32->no_fusion = value != 0;
-            if (p->w64) p->w64->no_fusion = value != 0;
-            if (p->i32) p->i32->no_fusion = value != 0;
-            if (p->i64) p->i64->no_fusion = value != 0;
-            if (p->x32) p->x32->inner.no_fusion = value != 0;
-            if (p->x64) p->x64->inner.no_fusion = value != 0;
-            if (p->s32) p->s32->no_fusion = value != 0;
-            if (p->s64) p->s64->no_fusion = value != 0;
-            if (p->c32) p->c32->no_fusion = value != 0;
-            if (p->c64) p->c64->no_fusion = value != 0;
-            if (p->q32) p->q32->no_fusion = value != 0;
-            if (p->q64) p->q64->no_fusion = value != 0;
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->w32 || p->w64 || p->i32 || p->i64 || p->x32 || p->x64 || p->s32 || p->s64 || p->c32 || p->c64 ||
-                    p->q32 || p->q64) ? 0 : -1;
-        case FFT_GPU_OPT_NO_CHAIN: {  // 0 the planner's rule, 1 never, 2 wherever the tiles agree (tools: the size rule is a measured one)
-            auto set = [&](auto* q) {
-                if (!q) return;
-                q->no_chain = value == 1;
-                q->core.chain_min_log2n = value == 2 ? 0 : std::remove_reference_t<decltype(q->core)>::kChainMinLog2n;
-            };
-            set(p->b32); set(p->b64); set(p->f32); set(p->f64); set(p->s32); set(p->s64);
-            return (p->b32 || p->b64 || p->f32 || p->f64 || p->s32 || p->s64) ? 0 : -1;
-        }
+            for_live_plan(p, [&](auto* q) {
+                if constexpr (takes_no_fusion<decltype(*q)>::value) { q->set_no_fusion(value != 0); rc = 0; }
+            });
+            return rc;
+        case FFT_GPU_OPT_NO_CHAIN:  // 0 the planner's rule, 1 never, 2 wherever the tiles agree
+            for_live_plan(p, [&](auto* q) {
+                if constexpr (takes_no_chain<decltype(*q)>::value) { q->set_no_chain(value); rc = 0; }
+            });
+            return rc;
         default:
             return -1;
     }
@@ -1598,20 +1326,12 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
             for (size_t i = 0; i < core->passes.size() && i < 4; i++) info->factors[i] = 1 << core->passes[i].log2L;
         }
     };
-    if (p->p32) fill(p->p32);
-    if (p->p64) fill(p->p64);
-    if (p->b32) {
-        fill(&p->b32->core);
-        info->bluestein_m = 1 << p->b32->log2m;
-        info->fused = (p->b32->core.hook_capable() && !p->b32->no_fusion) ? ((!p->b32->no_chain && p->b32->core.round_capable()) ? 3 : (!p->b32->no_chain && p->b32->core.chain_capable()) ? 2 : 1) : 0;
-        info->workspace_bytes += (size_t)p->batch * ((size_t)1 << p->b32->log2m) * sizeof(complex32_t);
-    }
-    if (p->b64) {
-        fill(&p->b64->core);
-        info->bluestein_m = 1 << p->b64->log2m;
-        info->fused = (p->b64->core.hook_capable() && !p->b64->no_fusion) ? ((!p->b64->no_chain && p->b64->core.round_capable()) ? 3 : (!p->b64->no_chain && p->b64->core.chain_capable()) ? 2 : 1) : 0;
-        info->workspace_bytes += (size_t)p->batch * ((size_t)1 << p->b64->log2m) * sizeof(complex_t);
-    }
+    auto fill_blue = [&](auto* b) {
+        fill(&b->core);
+        info->bluestein_m = 1 << b->log2m;
+        info->fused = (b->core.hook_capable() && !b->no_fusion) ? ((!b->no_chain && b->core.round_capable()) ? 3 : (!b->no_chain && b->core.chain_capable()) ? 2 : 1) : 0;
+        info->workspace_bytes += (size_t)p->batch * ((size_t)1 << b->log2m) * sizeof(*b->work);
+    };
     auto fill_mixed = [&](auto* m) {
         info->algo = ffteng::ALGO_MIXED_RADIX;
         info->n_passes = (int)m->passes.size();
@@ -1620,15 +1340,11 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         info->chunk_batch = m->chunk;
         info->workspace_bytes += m->scratch_bytes;
     };
-    if (p->m32) fill_mixed(p->m32);
-    if (p->m64) fill_mixed(p->m64);
     auto fill_fused = [&](auto* f) {  // fused consumers: the padded transform behind them
         fill(&f->core);
         const bool pair = !f->no_chain && f->kind != ffteng::FUSED_PSD;
         info->fused = f->fused() ? ((pair && f->kind != ffteng::FUSED_XCORR && f->core.round_capable()) ? 3 : (pair && f->core.chain_capable()) ? 2 : 1) : 0;
     };
-    if (p->f32) fill_fused(p->f32);
-    if (p->f64) fill_fused(p->f64);
     auto fill_frames = [&](auto* w) {  // n, batch = signals * frames, the core's passes; fused: framed load and stores ride on the pass
         fill(&w->core);
         info->fused = w->fused() ? 1 : 0;
@@ -1637,29 +1353,21 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (w->zwork) info->workspace_bytes += (size_t)w->frames() * (size_t)(w->n / 2) * sizeof(*w->zwork);
         if (w->xwork) info->workspace_bytes += (size_t)w->frames() * (size_t)w->bins() * sizeof(*w->xwork);
     };
-    if (p->w32) fill_frames(p->w32);
-    if (p->w64) fill_frames(p->w64);
     auto fill_iframes = [&](auto* w) {  // n, batch = signals * frames, the half-length core's passes; fused: the merge rides on the pass's load
         fill(&w->core);
         info->fused = w->fused() ? 1 : 0;
         info->workspace_bytes += (size_t)w->frames() * (size_t)(w->n / 2) * sizeof(*w->work);
     };
-    if (p->i32) fill_iframes(p->i32);
-    if (p->i64) fill_iframes(p->i64);
     auto fill_cross = [&](auto* c) {  // n, batch = signals * frames, the inner frames plan's core and path; chunk_batch: frames per chunk of the reduction
         fill_frames(&c->inner);
         info->chunk_batch = c->C;
         info->workspace_bytes += 2 * c->rows_bytes() + c->part_bytes();
     };
-    if (p->x32) fill_cross(p->x32);
-    if (p->x64) fill_cross(p->x64);
     auto fill_filter = [&](auto* f) {  // n = the block length, batch = signals * blocks, the core's passes; fused: 3 the one-launch path, else the fallback's middle
         fill(&f->core);
         info->fused = f->path();
         if (f->work) info->workspace_bytes += (size_t)2 * (size_t)f->chunk_blocks * (size_t)f->n * sizeof(*f->work);
     };
-    if (p->s32) fill_filter(p->s32);
-    if (p->s64) fill_filter(p->s64);
     // 2D convolution: n = Q, batch = matrices, factors = {Q, P, Q}; n_passes = HBM round trips of the work image (3 the column round, 5 the
     // padded fallback); fused: 1 the column round kernel runs
     auto fill_conv2d = [&](auto* c) {
@@ -1675,8 +1383,15 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (c->work2) info->workspace_bytes += m * (size_t)c->out_rows * q * esz;
         if (c->fwork) info->workspace_bytes += m * (size_t)c->P * q * esz;
     };
-    if (p->c32) fill_conv2d(p->c32);
-    if (p->c64) fill_conv2d(p->c64);
+    // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
+    auto fill_any = [&](auto* a) {
+        if (a->p2) fill(a->p2);
+        if (a->mr) fill_mixed(a->mr);
+        if (a->bl) {
+            fill(&a->bl->core);
+            info->bluestein_m = 1 << a->bl->log2m;
+        }
+    };
     // real 2D: n = cols, batch = matrices, factors = {cols, rows}; n_passes = 2 launches fused, else the fallback's steps (the row plan;
     // transpose, column plan, transpose); fused: 1 the hooked rows kernel and the column pass kernel run; algo / chunk_batch: the row core's
     auto fill_real2d = [&](auto* q) {
@@ -1693,20 +1408,7 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (q->fwork) info->workspace_bytes += q->spec_bytes();
         if (q->tbuf) info->workspace_bytes += q->spec_bytes();
     };
-    if (p->q32) fill_real2d(p->q32);
-    if (p->q64) fill_real2d(p->q64);
-    // a batched 1D transform of any length inside a 2D or real plan: its power-of-two core, or Bluestein's
-    auto fill_any = [&](auto* a) {
-        if (a->p2) fill(a->p2);
-        if (a->mr) fill_mixed(a->mr);
-        if (a->bl) {
-            fill(&a->bl->core);
-            info->bluestein_m = 1 << a->bl->log2m;
-        }
-    };
     auto fill_real = [&](auto* r) { fill_any(&r->core); };  // r2c / c2r: the half-length (even n) or full-length complex core
-    if (p->r32) fill_real(p->r32);
-    if (p->r64) fill_real(p->r64);
     // 2D: algo, chunk_batch, bluestein_m describe the row transforms; n_passes / factors the strided column passes
     // (1 direct, 2 two strided passes, 0: columns on the transposed image, or a single row)
     auto fill_2d = [&](auto* d) {
@@ -1718,8 +1420,20 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (d->tbuf) info->workspace_bytes += (size_t)d->rows * (size_t)d->cols * (size_t)d->max_matrices * sizeof(*d->tbuf);
         if (d->colt && d->colt->mr) info->workspace_bytes += d->colt->mr->scratch_bytes;  // (a two-pass mixed-radix plan on the transposed image)
     };
-    if (p->d32) fill_2d(p->d32);
-    if (p->d64) fill_2d(p->d64);
+    with_set(p, [&](auto& s) {  // one fill per member of the set
+        if (s.pow2) fill(s.pow2);
+        if (s.blue) fill_blue(s.blue);
+        if (s.mixed) fill_mixed(s.mixed);
+        if (s.two_d) fill_2d(s.two_d);
+        if (s.real) fill_real(s.real);
+        if (s.fused) fill_fused(s.fused);
+        if (s.frames) fill_frames(s.frames);
+        if (s.iframes) fill_iframes(s.iframes);
+        if (s.cross) fill_cross(s.cross);
+        if (s.filter) fill_filter(s.filter);
+        if (s.conv2d) fill_conv2d(s.conv2d);
+        if (s.real2d) fill_real2d(s.real2d);
+    });
     return 0;
 }
 

@@ -26,6 +26,10 @@ class AnyPlan {
     BluesteinPlan<T, RT>* bl = nullptr;
     MixedRadixPlan<T, RT>* mr = nullptr;
     ~AnyPlan() { delete p2; delete bl; delete mr; }
+    template <class F> void each_core(F&& f) {
+        if (p2) p2->each_core(f);
+        if (bl) bl->each_core(f);
+    }
     bool build(RT* rt, int n_, int dir_, int batch, int algo = ALGO_AUTO, bool smooth = false) {
         n = n_;
         dir = dir_ < 0 ? -1 : 1;
@@ -86,6 +90,11 @@ class Plan2D {
         delete colp;
         delete colt;
         if (rt && tbuf) rt->dfree(tbuf);
+    }
+    template <class F> void each_core(F&& f) {
+        rowp.each_core(f);
+        if (colp) f(colp);
+        if (colt) colt->each_core(f);
     }
     bool build(RT* runtime, int rows_, int cols_, int dir_, int n_matrices, bool smooth = false) {
         rt = runtime; rows = rows_; cols = cols_; dir = dir_ < 0 ? -1 : 1; max_matrices = n_matrices;
@@ -158,6 +167,7 @@ class RealPlan {
         if (rt && w) rt->dfree(w);
         if (rt && work) rt->dfree(work);
     }
+    template <class F> void each_core(F&& f) { core.each_core(f); }
     bool even() const { return (n & 1) == 0; }
     bool build(RT* runtime, int n_, bool r2c, int batch, bool smooth = false) {
         rt = runtime; n = n_; forward = r2c; max_batch = batch; h = n / 2;
@@ -214,6 +224,39 @@ class RealPlan {
 //   PSD            one-sided periodogram of Hann-windowed x[b]: [batch][n/2 + 1] real
 // ---------------------------------------------------------------------------
 enum FusedKind { FUSED_CONV_LINEAR = 0, FUSED_CONV_CIRCULAR = 1, FUSED_AUTOCORR = 2, FUSED_XCORR = 3, FUSED_PSD = 4 };
+enum FramesWindow { WINDOW_RECT = 0, WINDOW_HANN = 1, WINDOW_HAMMING = 2, WINDOW_BLACKMAN = 3, WINDOW_USER = 4 };
+
+// The windows of the periodogram and the frames plans: the reference's formulas with their n - 1 denominators
+// (power_spectrum.c:5-25), n values in long double; every caller rounds them to T and packs them its own way.  A window of one
+// sample is 1, not 0 / 0.  w_host: the n values of WINDOW_USER, unused otherwise
+template <typename T>
+static std::vector<long double> window_values(int window, int n, const T* w_host) {
+    std::vector<long double> w((size_t)n, 1.0L);
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    for (int i = 0; i < n; i++) {
+        if (window == WINDOW_USER) w[(size_t)i] = (long double)w_host[i];
+        if (window == WINDOW_USER || window == WINDOW_RECT || n == 1) continue;
+        const long double a = two_pi * (long double)i / (long double)(n - 1);
+        if (window == WINDOW_HANN) w[(size_t)i] = 0.5L * (1.0L - cosl(a));
+        else if (window == WINDOW_HAMMING) w[(size_t)i] = 0.54L - 0.46L * cosl(a);
+        else if (window == WINDOW_BLACKMAN) w[(size_t)i] = 0.42L - 0.5L * cosl(a) + 0.08L * cosl(2.0L * a);
+    }
+    return w;
+}
+
+// The spectrum of a kernel fixed at plan time: its nh values zero padded to the core's length m, uploaded and transformed once by
+// the plan's own core.  nullptr: no device memory
+template <typename T, typename RT>
+static cpx<T>* kernel_spectrum(RT* rt, Pow2Plan<T, RT>& core, const cpx<T>* h_host, int nh, long long m) {
+    std::vector<cpx<T>> hp((size_t)m);
+    for (auto& z : hp) { z.re = 0; z.im = 0; }
+    for (int i = 0; i < nh; i++) hp[(size_t)i] = h_host[i];
+    cpx<T>* H = (cpx<T>*)rt->dmalloc((size_t)m * sizeof(cpx<T>));
+    if (!H) return nullptr;
+    rt->h2d(H, hp.data(), (size_t)m * sizeof(cpx<T>));
+    core.execute(H, H, 1, false);
+    return H;
+}
 
 template <typename T, typename RT>
 class FusedPlan {
@@ -232,6 +275,9 @@ class FusedPlan {
         if (!rt) return;
         rt->dfree(H); rt->dfree(work); rt->dfree(work2);
     }
+    template <class F> void each_core(F&& f) { f(&core); }
+    void set_no_fusion(bool v) { no_fusion = v; }
+    void set_no_chain(int v) { no_chain = v == 1; core.set_chain_rule(v == 2); }  // (BluesteinPlan::set_no_chain)
     long long m() const { return 1ll << log2m; }
     int out_len() const { return kind == FUSED_PSD ? nx / 2 + 1 : ny; }
 
@@ -273,19 +319,14 @@ class FusedPlan {
             if (!work2) return false;
         }
         if (kind == FUSED_CONV_LINEAR || kind == FUSED_CONV_CIRCULAR) {
-            std::vector<cpx<T>> hp((size_t)mm);
-            for (auto& z : hp) { z.re = 0; z.im = 0; }
-            for (int i = 0; i < nh; i++) hp[(size_t)i] = h_host[i];
-            H = (cpx<T>*)rt->dmalloc((size_t)mm * SZ);
+            H = kernel_spectrum(rt, core, h_host, nh, mm);
             if (!H) return false;
-            rt->h2d(H, hp.data(), (size_t)mm * SZ);
-            core.execute(H, H, 1, false);  // the kernel's spectrum, once
         } else if (kind == FUSED_PSD) {
-            // Hann window 0.5 (1 - cos(2 pi i / (n - 1))) (power_spectrum.c:5-10), as complex values; + 1 padding entry
+            // the Hann window as complex values; + 1 padding entry
             std::vector<cpx<T>> wv((size_t)nx + 1);
-            const long double two_pi = 6.283185307179586476925286766559005768L;
+            const std::vector<long double> hann = window_values<T>(WINDOW_HANN, nx, nullptr);
             for (int i = 0; i < nx; i++) {
-                wv[(size_t)i].re = nx > 1 ? (T)(0.5L * (1.0L - cosl(two_pi * (long double)i / (long double)(nx - 1)))) : (T)1;
+                wv[(size_t)i].re = (T)hann[(size_t)i];
                 wv[(size_t)i].im = 0;
             }
             wv[(size_t)nx] = wv[0];
@@ -410,7 +451,6 @@ class FusedPlan {
 //   no_fusion: frames_pack_real_kernel (windowed frames -> [frames][L] complex), the plain core, r2c_split_kernel, and for POWER /
 //   WELCH psd_onesided_rows_kernel -- correct, not tuned.
 // ---------------------------------------------------------------------------
-enum FramesWindow { WINDOW_RECT = 0, WINDOW_HANN = 1, WINDOW_HAMMING = 2, WINDOW_BLACKMAN = 3, WINDOW_USER = 4 };
 enum FramesOut { FRAMES_STFT = 0, FRAMES_POWER = 1, FRAMES_WELCH = 2 };
 
 template <typename T, typename RT>
@@ -435,6 +475,8 @@ class FramesPlan {
         if (!rt) return;
         rt->dfree(win); rt->dfree(power); rt->dfree(work); rt->dfree(wsplit); rt->dfree(zwork); rt->dfree(xwork);
     }
+    template <class F> void each_core(F&& f) { f(&core); }
+    void set_no_fusion(bool v) { no_fusion = v; }
     long long frames() const { return (long long)n_signals * nw; }
     int bins() const { return n / 2 + 1; }
     bool fused() const { return ok && !no_fusion && core.round_capable() && core.frames_exact(frames(), nw); }
@@ -450,19 +492,13 @@ class FramesPlan {
         if (nw < 1 || frames() > 0x7fffffff || frames() * (long long)n > (1ll << 40)) return false;
         core.wants_hooks = true;
         if (!core.build(rt, ilog2(real_input ? n / 2 : n), ALGO_AUTO, (int)frames())) return false;
-        // the reference's windows with their n - 1 denominators (power_spectrum.c:5-25), as complex values; + 1 padding entry
+        // the window as complex values; + 1 padding entry
         std::vector<cpx<T>> wv((size_t)n + 1);
-        const long double two_pi = 6.283185307179586476925286766559005768L;
+        const std::vector<long double> wl = window_values(window, n, w_host);
         long double sum2 = 0.0L;
         for (int i = 0; i < n; i++) {
-            const long double a = two_pi * (long double)i / (long double)(n - 1);
-            long double w = 1.0L;
-            if (window == WINDOW_HANN) w = 0.5L * (1.0L - cosl(a));
-            else if (window == WINDOW_HAMMING) w = 0.54L - 0.46L * cosl(a);
-            else if (window == WINDOW_BLACKMAN) w = 0.42L - 0.5L * cosl(a) + 0.08L * cosl(2.0L * a);
-            else if (window == WINDOW_USER) w = (long double)w_host[i];
-            sum2 += w * w;
-            wv[(size_t)i].re = (T)w;
+            sum2 += wl[(size_t)i] * wl[(size_t)i];
+            wv[(size_t)i].re = (T)wl[(size_t)i];
             wv[(size_t)i].im = 0;
         }
         wv[(size_t)n] = wv[0];
@@ -607,6 +643,8 @@ class IFramesPlan {
         if (!rt) return;
         rt->dfree(win); rt->dfree(inv_env); rt->dfree(wmerge); rt->dfree(work);
     }
+    template <class F> void each_core(F&& f) { f(&core); }
+    void set_no_fusion(bool v) { no_fusion = v; }
     long long frames() const { return (long long)n_signals * nw; }
     long long out_len() const { return (long long)(nw - 1) * hop + n; }
     bool fused() const { return ok && !no_fusion && core.round_capable(); }
@@ -620,19 +658,13 @@ class IFramesPlan {
         const int h = n / 2;
         core.wants_hooks = true;
         if (!core.build(rt, ilog2(h), ALGO_AUTO, (int)frames())) return false;
-        // the frames plans' windows (the reference's formulas with their n - 1 denominators, power_spectrum.c:5-25) as reals of T;
-        // the envelope is built from those ROUNDED values -- the ones the kernels multiply by -- in long double
+        // the frames plans' windows as reals of T; the envelope is built from those ROUNDED values -- the ones the kernels multiply
+        // by -- in long double
         std::vector<T> g((size_t)n);
-        const long double two_pi = 6.283185307179586476925286766559005768L;
+        const std::vector<long double> wl = window_values(window, n, w_host);
         long double gmax2 = 0.0L;
         for (int i = 0; i < n; i++) {
-            const long double a = two_pi * (long double)i / (long double)(n - 1);
-            long double w = 1.0L;
-            if (window == WINDOW_HANN) w = 0.5L * (1.0L - cosl(a));
-            else if (window == WINDOW_HAMMING) w = 0.54L - 0.46L * cosl(a);
-            else if (window == WINDOW_BLACKMAN) w = 0.42L - 0.5L * cosl(a) + 0.08L * cosl(2.0L * a);
-            else if (window == WINDOW_USER) w = (long double)w_host[i];
-            g[(size_t)i] = (T)w;
+            g[(size_t)i] = (T)wl[(size_t)i];
             const long double g2 = (long double)g[(size_t)i] * (long double)g[(size_t)i];
             if (g2 > gmax2) gmax2 = g2;
         }
@@ -732,6 +764,9 @@ class FilterPlan {
         if (!rt) return;
         rt->dfree(H); rt->dfree(work);
     }
+    template <class F> void each_core(F&& f) { f(&core); }
+    void set_no_fusion(bool v) { no_fusion = v; }
+    void set_no_chain(int v) { no_chain = v == 1; core.set_chain_rule(v == 2); }  // (BluesteinPlan::set_no_chain)
     long long blocks() const { return (long long)n_signals * nb; }
     static int choose_n(int n_taps) {
         long long want = 1;
@@ -774,13 +809,8 @@ class FilterPlan {
         // a block length above kNmax never takes the one-launch path and only ever runs on chunks: its (multi-pass) core and the
         // scratch images that core owns are sized for one chunk, not for the whole execute
         if (!core.build(rt, ilog2(n), ALGO_AUTO, n > kNmax ? chunk_blocks : (int)blocks())) return false;
-        std::vector<cpx<T>> hp((size_t)n);
-        for (auto& z : hp) { z.re = 0; z.im = 0; }
-        for (int i = 0; i < n_taps; i++) hp[(size_t)i] = h_host[i];
-        H = (cpx<T>*)rt->dmalloc((size_t)n * SZ);
+        H = kernel_spectrum(rt, core, h_host, n_taps, n);
         if (!H) return false;
-        rt->h2d(H, hp.data(), (size_t)n * SZ);
-        core.execute(H, H, 1, false);  // the taps' spectrum, once
         ok = true;
         return true;
     }
@@ -892,6 +922,9 @@ class ColRoundStep {
     Pow2Plan<T, RT> colp;  // build_columns: the tile and the stage tables
     int log2P = 0, Q = 0;
     bool ok = false;
+    template <class F> void each_core(F&& f) {
+        if (colp.ok) f(&colp);
+    }
     bool build(RT* runtime, int log2P_, int Q_, int n_matrices, int min_seg_bytes) {
         rt = runtime; log2P = log2P_; Q = Q_;
         if (!colp.build_columns(rt, log2P, Q, n_matrices)) return false;
@@ -946,6 +979,13 @@ class Conv2DPlan {
         if (!rt) return;
         rt->dfree(H); rt->dfree(work1); rt->dfree(work2); rt->dfree(fwork);
     }
+    template <class F> void each_core(F&& f) {
+        f(&rowp);
+        round.each_core(f);
+        if (fwd) fwd->each_core(f);  // (the fallback's plans: once an execute has made them)
+        if (inv) inv->each_core(f);
+    }
+    void set_no_fusion(bool v) { no_fusion = v; }
     bool fusable() const { return ok && round.ok && rowp.ok && rowp.hook_capable() && work1 && work2; }
     bool fused() const { return fusable() && !no_fusion; }
     int passes() const { return fused() ? 3 : 5; }  // HBM round trips of the work image
@@ -1126,6 +1166,8 @@ class CrossFramesPlan {
         if (!rt) return;
         rt->dfree(rows_x); rt->dfree(rows_y); rt->dfree(part);
     }
+    template <class F> void each_core(F&& f) { inner.each_core(f); }
+    void set_no_fusion(bool v) { inner.set_no_fusion(v); }
     static int chunk_len(int nw, int n_signals, int hb) {
         const long long per_chunk = (long long)n_signals * hb;
         const long long want = (kTargetThreads + per_chunk - 1) / per_chunk;
@@ -1231,6 +1273,9 @@ class ColPassStep {
     Pow2Plan<T, RT> colp;  // build_columns: the tile and the stage tables
     int log2P = 0, n_cols = 0, n_ct = 0;
     bool ok = false;
+    template <class F> void each_core(F&& f) {
+        if (colp.ok) f(&colp);
+    }
     // the tile is that of the n_cols - 1 columns before the last (rounded down to the 16-byte lane access): for the L + 1 columns of
     // a real image's row spectra C divides L, and the last tile of every matrix holds exactly one live column
     bool build(RT* runtime, int log2P_, int n_cols_, int n_matrices, int min_seg_bytes) {
@@ -1301,6 +1346,13 @@ class Real2DPlan {
         if (!rt) return;
         rt->dfree(wtab); rt->dfree(work); rt->dfree(rout); rt->dfree(fwork); rt->dfree(tbuf); rt->dfree(rstage);
     }
+    template <class F> void each_core(F&& f) {
+        if (core.ok) f(&core);
+        cstep.each_core(f);
+        if (rp) rp->each_core(f);  // (the fallback's plans: once the build or an execute has made them)
+        if (colt) colt->each_core(f);
+    }
+    void set_no_fusion(bool v) { no_fusion = v; }
     long long frames() const { return (long long)rows * n_matrices; }
     bool fusable() const { return ok && cstep.ok && core.ok && core.round_capable() && core.frames_exact(frames(), rows) && work && wtab; }
     bool fused() const { return fusable() && !no_fusion; }
