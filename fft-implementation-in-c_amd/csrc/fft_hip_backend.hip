@@ -318,9 +318,11 @@ struct PlanSet {
     ffteng::FilterPlan<T, HipRT>* filter = nullptr;         // overlap-save FIR filtering of long signals
     ffteng::Conv2DPlan<T, HipRT>* conv2d = nullptr;         // 2D convolution / spectrum filtering of images
     ffteng::Real2DPlan<T, HipRT>* real2d = nullptr;         // rfft2 / irfft2 of real images
+    ffteng::DctPlan<T, HipRT>* dct = nullptr;               // DCT / DST of types II and III on batched real rows
+    ffteng::Dct2DPlan<T, HipRT>* dct2d = nullptr;           // ... along both axes of real images
     template <class F>
     void each(F&& f) {
-        f(pow2); f(blue); f(mixed); f(two_d); f(real); f(fused); f(frames); f(iframes); f(cross); f(filter); f(conv2d); f(real2d);
+        f(pow2); f(blue); f(mixed); f(two_d); f(real); f(fused); f(frames); f(iframes); f(cross); f(filter); f(conv2d); f(real2d); f(dct); f(dct2d);
     }
     // a caller's untyped array as complex / real values of this precision
     static const fftk::cpx<T>* c(const void* v) { return (const fftk::cpx<T>*)v; }
@@ -342,7 +344,7 @@ struct fft_gpu_plan {
     PlanSet<double> set64;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11, PLAN_DCT = 12, PLAN_DCT_2D = 13 };
 
 namespace {
 
@@ -988,6 +990,36 @@ int fft_gpu_execute_real2d_hip(fft_gpu_plan_t p, const void* d_in, long long in_
     return run_on_device(p, [&](auto& s) { return s.real2d->execute(d_in, in_pitch, d_out, out_pitch); });
 }
 
+// cosine / sine transforms of types II and III (fft_plans_ext.h DctPlan, Dct2DPlan)
+static bool dct_args_ok(fft_gpu_dct_t type, fft_gpu_dct_norm_t norm) { return (int)type >= 0 && (int)type <= 3 && (int)norm >= 0 && (int)norm <= 2; }
+fft_gpu_plan_t fft_gpu_plan_dct_hip(int n, int batch, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec) {
+    if (n <= 0 || batch <= 0 || !dct_args_ok(type, norm) || (long long)n * batch > 0x7fffffffll) {
+        fprintf(stderr, "fft_hip: invalid DCT plan arguments (n=%d batch=%d type=%d norm=%d)\n", n, batch, (int)type, (int)norm);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(n, batch, ((int)type & 1) ? 1 : -1, prec, PLAN_DCT);
+    if (!p) return NULL;
+    return make_plan(p, "DCT", [&](auto& s) { return construct(p, s.dct, n, batch, (int)type, (int)norm); });
+}
+fft_gpu_plan_t fft_gpu_plan_dct_2d_hip(int rows, int cols, int n_matrices, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec) {
+    if (rows <= 0 || cols <= 0 || n_matrices <= 0 || !dct_args_ok(type, norm) || (long long)rows * cols > (1ll << 30) ||
+        (long long)rows * cols * n_matrices > 0x7fffffffll) {
+        fprintf(stderr, "fft_hip: invalid 2D DCT plan arguments (rows=%d cols=%d matrices=%d type=%d norm=%d)\n", rows, cols, n_matrices, (int)type, (int)norm);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(cols, n_matrices, ((int)type & 1) ? 1 : -1, prec, PLAN_DCT_2D);
+    if (!p) return NULL;
+    p->rows = rows; p->cols = cols;
+    return make_plan(p, "2D DCT", [&](auto& s) { return construct(p, s.dct2d, rows, cols, n_matrices, (int)type, (int)norm); });
+}
+// async on the plan's stream.  Pitches in reals between rows (1D) or matrices (2D), 0: dense; d_in == d_out is allowed
+int fft_gpu_execute_dct_hip(fft_gpu_plan_t p, const void* d_in, long long in_pitch, void* d_out, long long out_pitch) {
+    if (!p || !d_in || !d_out || (p->kind != PLAN_DCT && p->kind != PLAN_DCT_2D)) return -1;
+    return run_on_device(p, [&](auto& s) {
+        return p->kind == PLAN_DCT ? s.dct->execute(s.r(d_in), in_pitch, s.r(d_out), out_pitch) : s.dct2d->execute(s.r(d_in), in_pitch, s.r(d_out), out_pitch);
+    });
+}
+
 int fft_gpu_plan_set_stream_hip(fft_gpu_plan_t p, void* hip_stream) {
     if (!p) return -1;
     (void)hipStreamSynchronize(p->rt.stream);
@@ -1408,6 +1440,26 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (q->fwork) info->workspace_bytes += q->spec_bytes();
         if (q->tbuf) info->workspace_bytes += q->spec_bytes();
     };
+    // DCT / DST: n = N, batch, the passes and factors of the core (fused: the half-length single pass; else the fallback's length-N plan)
+    auto fill_dct = [&](auto* q) {
+        if (q->fusable()) fill(&q->core);
+        else if (q->full) fill_any(q->full);
+        info->n = q->n;
+        info->batch = q->batch;
+        info->fused = q->fused() ? 1 : 0;
+        if (q->work) info->workspace_bytes += (size_t)q->batch * (size_t)q->n * sizeof(*q->work);
+    };
+    // 2D: n = cols, batch = matrices, the row plan's core, factors = {cols, rows}; n_passes = the composition's 4 steps
+    auto fill_dct2d = [&](auto* q) {
+        fill_dct(&q->rowp);
+        info->n = q->cols;
+        info->batch = q->n_matrices;
+        info->n_passes = 4;
+        info->factors[0] = q->cols; info->factors[1] = q->rows; info->factors[2] = 0; info->factors[3] = 0;
+        info->fused = q->fused() ? 1 : 0;
+        info->workspace_bytes += (size_t)2 * (size_t)q->n_matrices * (size_t)q->rows * (size_t)q->cols * sizeof(*q->t1);
+        if (q->colp.work) info->workspace_bytes += (size_t)q->colp.batch * (size_t)q->colp.n * sizeof(*q->colp.work);
+    };
     auto fill_real = [&](auto* r) { fill_any(&r->core); };  // r2c / c2r: the half-length (even n) or full-length complex core
     // 2D: algo, chunk_batch, bluestein_m describe the row transforms; n_passes / factors the strided column passes
     // (1 direct, 2 two strided passes, 0: columns on the transposed image, or a single row)
@@ -1433,6 +1485,8 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (s.filter) fill_filter(s.filter);
         if (s.conv2d) fill_conv2d(s.conv2d);
         if (s.real2d) fill_real2d(s.real2d);
+        if (s.dct) fill_dct(s.dct);
+        if (s.dct2d) fill_dct2d(s.dct2d);
     });
     return 0;
 }

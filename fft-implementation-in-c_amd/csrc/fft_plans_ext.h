@@ -1,8 +1,8 @@
 // fft_plans_ext.h -- plans built ON the batched 1D engine (fft_engine.h) for the "next" rows of the scope table
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
-// overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, 2D convolution / spectrum filtering, and the real 2D
-// transforms rfft2 / irfft2).  Templated on the same runtime policy RT as the engine, so the
+// overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, 2D convolution / spectrum filtering, the real 2D
+// transforms rfft2 / irfft2, and the cosine / sine transforms of types II and III).  Templated on the same runtime policy RT as the engine, so the
 // unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
@@ -10,6 +10,7 @@
 #include "fft_kernels_ext.h"
 #include "fft_kernels_conv2d.h"
 #include "fft_kernels_real2d.h"
+#include "fft_kernels_dct.h"
 
 namespace ffteng {
 
@@ -1497,6 +1498,226 @@ class Real2DPlan {
             rp->execute_c2r(fwork, direct ? x_out : rstage, nf);
             if (!direct) copy<T>(rstage, rm, x_out, out_pitch, rm);
         }
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Cosine and sine transforms of types II and III of batched real rows, scipy.fft's dct / idct / dst / idst (the reference's
+// applications/image_fft.c names the DCT as the transform behind image compression and has none):
+//   DCT-II   X[k] = 2 sum_n x[n] cos(pi k (2n+1) / 2N)          DCT-III  y[n] = X[0] + 2 sum_{k>=1} X[k] cos(pi k (2n+1) / 2N)
+//   DST-II   X[k] = 2 sum_n x[n] sin(pi (k+1)(2n+1) / 2N)       DST-III  y[n] = (-1)^n X[N-1] + 2 sum_{k<N-1} X[k] sin(pi (2n+1)(k+1) / 2N)
+// norm: NONE as above; INVERSE times 1 / (2N) (DCT-III INVERSE = scipy's idct of type 2); ORTHO scipy's norm = "ortho" (the odd index
+// out is k = 0 for the cosine and k = N - 1 for the sine transforms).  The factors live in the plan's tables, made in long double and
+// rounded once.  Rows lie in_pitch / out_pitch reals apart (0: dense), at any sizeof(T)-aligned base.
+//
+// Fused path: ONE launch of dct_rows_kernel (fft_kernels_dct.h) for all rows, one HBM round trip of N reals per row, in place
+// allowed.  Taken where N is a power of two, a row is at least 64 bytes (N >= 16 fp32, 8 fp64) and L = N/2 fits ONE hook-capable pass
+// of the rows kernel up to kLmax (Real2DPlan's cap: what the real frames tests check).
+// Fallback (everything else, any N >= 1, and no_fusion; correct, not tuned): Makhoul's algorithm on a length-N complex transform --
+// dct_pre_kernel (permute, or twiddle into the Hermitian spectrum), AnyPlan on a work image of the plan's own, dct_post_kernel.
+// ---------------------------------------------------------------------------
+enum { DCT_II = 0, DCT_III = 1, DST_II = 2, DST_III = 3 };
+enum { DCT_NORM_NONE = 0, DCT_NORM_INVERSE = 1, DCT_NORM_ORTHO = 2 };
+
+template <typename T, typename RT>
+class DctPlan {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    static constexpr int kLmax = Real2DPlan<T, RT>::kLmax;
+    RT* rt = nullptr;
+    int n = 0, batch = 0, type = 0, norm = 0;
+    int L = 0;
+    Pow2Plan<T, RT> core;           // fused: length L, the tile and the stage tables of the hooked rows kernel
+    cpx<T>* ta = nullptr;           // fused: fftk::DctParams::ta / tb
+    cpx<T>* tb = nullptr;
+    AnyPlan<T, RT>* full = nullptr; // fallback (made at its first use): length n
+    cpx<T>* ftab = nullptr;         // fallback: [n]
+    cpx<T>* work = nullptr;         // fallback: [batch][n]
+    bool ok = false;
+    bool no_fusion = false;
+    ~DctPlan() {
+        delete full;
+        if (!rt) return;
+        rt->dfree(ta); rt->dfree(tb); rt->dfree(ftab); rt->dfree(work);
+    }
+    template <class F> void each_core(F&& f) {
+        if (core.ok) f(&core);
+        if (full) full->each_core(f);
+    }
+    void set_no_fusion(bool v) { no_fusion = v; }
+    bool inverse() const { return (type & 1) != 0; }
+    bool sine() const { return (type & 2) != 0; }
+    bool fusable() const { return ok && core.ok && core.round_capable() && ta && tb; }
+    bool fused() const { return fusable() && !no_fusion; }
+
+    // f_k (forward: on output k) or g_k (inverse: on input k) of the cosine transform the plan runs; k = 0 is ORTHO's odd index out
+    long double factor(int k) const {
+        const long double N = (long double)n;
+        if (norm == DCT_NORM_INVERSE) return 1.0L / (2.0L * N);
+        if (norm == DCT_NORM_ORTHO) {
+            if (inverse()) return k == 0 ? 1.0L / sqrtl(N) : 1.0L / sqrtl(2.0L * N);
+            return k == 0 ? 1.0L / sqrtl(4.0L * N) : 1.0L / sqrtl(2.0L * N);
+        }
+        return 1.0L;
+    }
+    static cpx<T> rounded(long double re, long double im) {  // a table entry: made in long double, rounded once
+        cpx<T> c;
+        c.re = (T)re; c.im = (T)im;
+        return c;
+    }
+    cpx<T>* upload(const std::vector<cpx<T>>& t) {
+        cpx<T>* d = (cpx<T>*)rt->dmalloc(t.size() * SZ);
+        if (d) rt->h2d(d, t.data(), t.size() * SZ);
+        return d;
+    }
+
+    bool build(RT* runtime, int n_, int batch_, int type_, int norm_) {
+        rt = runtime; n = n_; batch = batch_; type = type_; norm = norm_;
+        if (n < 1 || batch < 1 || type < DCT_II || type > DST_III || norm < DCT_NORM_NONE || norm > DCT_NORM_ORTHO ||
+            (long long)n * batch > 0x7fffffffll) return false;
+        L = n / 2;
+        ok = true;
+        const long double pi = 3.141592653589793238462643383279502884L;
+        if ((n & (n - 1)) == 0 && (size_t)n * sizeof(T) >= 64 && L <= kLmax) {
+            core.wants_hooks = true;
+            if (core.build(rt, ilog2(L), ALGO_AUTO, batch) && core.round_capable()) {
+                std::vector<cpx<T>> a((size_t)L + 1), b((size_t)L + 1);
+                for (int k = 0; k <= L; k++) {
+                    const long double f = factor(k), tq = pi * k / (2.0L * n), tw = 2.0L * pi * k / n;
+                    if (!inverse()) {  // qa = f q, qb = f q W / i
+                        a[k] = rounded(f * cosl(tq), -f * sinl(tq));
+                        b[k] = rounded(-f * sinl(tq + tw), -f * cosl(tq + tw));
+                    } else {           // cq = g conj q, cw = conj W
+                        a[k] = rounded(f * cosl(tq), f * sinl(tq));
+                        b[k] = rounded(cosl(tw), sinl(tw));
+                    }
+                }
+                ta = upload(a); tb = upload(b);
+                if (!ta || !tb) { ok = false; return false; }
+            }
+        }
+        if (!fusable() && !ensure_fallback()) { ok = false; return false; }
+        return true;
+    }
+
+    bool ensure_fallback() {
+        if (!full) {
+            full = new AnyPlan<T, RT>();
+            if (!full->build(rt, n, inverse() ? 1 : -1, batch)) { delete full; full = nullptr; return false; }
+        }
+        if (!ftab) {
+            const long double pi = 3.141592653589793238462643383279502884L;
+            std::vector<cpx<T>> t((size_t)n);
+            for (int k = 0; k < n; k++) {
+                const long double tq = pi * k / (2.0L * n);
+                // forward: 2 f q;  inverse: n g conj q (AnyPlan's inverse carries 1 / n, Makhoul's is unscaled)
+                const long double f = inverse() ? factor(k) * (long double)n : 2.0L * factor(k);
+                t[k] = rounded(f * cosl(tq), (inverse() ? f : -f) * sinl(tq));
+            }
+            ftab = upload(t);
+        }
+        if (!work) work = (cpx<T>*)rt->dmalloc((size_t)batch * (size_t)n * SZ);
+        return ftab && work;
+    }
+
+    // 0 / -1 (bad arguments or a failed allocation: nothing is launched)
+    int execute(const T* in, long long in_pitch, T* out, long long out_pitch) {
+        if (!ok || !in || !out) return -1;
+        if (in_pitch == 0) in_pitch = n;
+        if (out_pitch == 0) out_pitch = n;
+        if (in_pitch < n || out_pitch < n) return -1;
+        if (fused()) {
+            const PassDesc& a = core.passes[0];
+            fftk::DctParams<T> q;
+            memset(&q, 0, sizeof(q));
+            q.in = in; q.out = out; q.tables = core.pass_tables[0]; q.ta = ta; q.tb = tb;
+            q.group_bytes = a.group_bytes; q.tables_bytes = a.tables_elems * SZ; q.off_tables = a.off_tables; q.o_sb = a.o_sb; q.sa_bits = a.sa_bits;
+            q.log2L = a.log2L; q.log2C = a.log2C;
+            q.in_pitch = in_pitch; q.out_pitch = out_pitch;
+            q.n_rows = batch;
+            q.n_tiles = ((long long)batch + (1ll << a.log2C) - 1) >> a.log2C;
+            q.in_vec = (((uintptr_t)in & 15) == 0 && (in_pitch * (long long)sizeof(T)) % 16 == 0) ? 1 : 0;
+            q.out_vec = (((uintptr_t)out & 15) == 0 && (out_pitch * (long long)sizeof(T)) % 16 == 0) ? 1 : 0;
+            q.sine = sine() ? 1 : 0;
+            if (inverse()) launch_rows(fftk::dct_rows_kernel<T, true>, q, a);
+            else launch_rows(fftk::dct_rows_kernel<T, false>, q, a);
+            return 0;
+        }
+        if (!ensure_fallback()) return -1;
+        const long long total = (long long)batch * n;
+        launch_flat(rt, fftk::dct_pre_kernel<T>, total, in, in_pitch, work, (const cpx<T>*)ftab, n, inverse() ? 1 : 0, sine() ? 1 : 0, total);
+        full->execute(work, work, batch);
+        launch_flat(rt, fftk::dct_post_kernel<T>, total, (const cpx<T>*)work, (const cpx<T>*)ftab, out, out_pitch, n, inverse() ? 1 : 0, sine() ? 1 : 0, total);
+        return 0;
+    }
+
+  private:
+    template <class K>
+    void launch_rows(K kernel, const fftk::DctParams<T>& q, const PassDesc& a) {
+        int per_cu = rt->max_blocks_per_cu(kernel, a.nthreads, (size_t)a.smem_bytes);
+        if (per_cu < 1) per_cu = 1;
+        long long grid = (long long)rt->num_cus() * per_cu;
+        if (grid > q.n_tiles) grid = q.n_tiles;
+        rt->launch(kernel, grid, a.nthreads, (size_t)a.smem_bytes, q);
+    }
+};
+
+// ---------------------------------------------------------------------------
+// The same transform along both axes of [M][rows][cols] real images, scipy's dctn / idctn over the last two axes.  Composition only:
+// the row plan on the rows, transpose_real_kernel, the row plan of length `rows` on the transposed image, transpose back.  Matrices lie
+// in_pitch / out_pitch reals apart (0: dense); the rows of a matrix are dense.  In place is allowed (everything in between happens in
+// images of the plan's own).
+// ---------------------------------------------------------------------------
+template <typename T, typename RT>
+class Dct2DPlan {
+  public:
+    RT* rt = nullptr;
+    int rows = 0, cols = 0, n_matrices = 0;
+    DctPlan<T, RT> rowp, colp;  // length cols on M * rows rows; length rows on M * cols rows
+    T* t1 = nullptr;            // [M][rows][cols]
+    T* t2 = nullptr;            // [M][cols][rows]
+    bool ok = false;
+    ~Dct2DPlan() {
+        if (!rt) return;
+        rt->dfree(t1); rt->dfree(t2);
+    }
+    template <class F> void each_core(F&& f) {
+        rowp.each_core(f);
+        colp.each_core(f);
+    }
+    void set_no_fusion(bool v) { rowp.set_no_fusion(v); colp.set_no_fusion(v); }
+    bool fused() const { return rowp.fused() && colp.fused(); }
+    bool build(RT* runtime, int rows_, int cols_, int n_matrices_, int type, int norm) {
+        rt = runtime; rows = rows_; cols = cols_; n_matrices = n_matrices_;
+        if (rows < 1 || cols < 1 || n_matrices < 1 || (long long)rows * cols > (1ll << 30) || (long long)rows * cols * n_matrices > 0x7fffffffll) return false;
+        if (!rowp.build(rt, cols, rows * n_matrices, type, norm) || !colp.build(rt, rows, cols * n_matrices, type, norm)) return false;
+        const size_t bytes = (size_t)n_matrices * (size_t)rows * (size_t)cols * sizeof(T);
+        t1 = (T*)rt->dmalloc(bytes);
+        t2 = (T*)rt->dmalloc(bytes);
+        ok = t1 && t2;
+        return ok;
+    }
+    void transpose(const T* in, long long in_b, T* out, long long out_b, int r, int c) {
+        const long long tiles = (long long)n_matrices * ((r + 31) / 32) * ((c + 31) / 32);
+        const long long grid = tiles > 65536 ? 65536 : tiles;
+        rt->launch(fftk::transpose_real_kernel<T>, grid, 256, (size_t)(32 * 33 * sizeof(T)), in, in_b, out, out_b, r, c, tiles);
+    }
+    int execute(const T* in, long long in_pitch, T* out, long long out_pitch) {
+        if (!ok || !in || !out) return -1;
+        const long long rm = (long long)rows * cols;
+        if (in_pitch == 0) in_pitch = rm;
+        if (out_pitch == 0) out_pitch = rm;
+        if (in_pitch < rm || out_pitch < rm) return -1;
+        if (in_pitch != rm) {  // the row plan takes ONE pitch between rows: matrices with a pitch of their own are gathered first
+            launch_flat(rt, fftk::real2d_copy_kernel<T>, rm * n_matrices, in, in_pitch, t1, rm, rm, rm * n_matrices);
+            in = t1;
+        }
+        if (rowp.execute(in, cols, t1, cols) != 0) return -1;
+        transpose(t1, rm, t2, rm, rows, cols);
+        if (colp.execute(t2, rows, t2, rows) != 0) return -1;
+        transpose(t2, rm, out, out_pitch, cols, rows);
         return 0;
     }
 };

@@ -22,6 +22,15 @@ ALGO_AUTO, ALGO_RADIX2, ALGO_RADIX4, ALGO_SPLIT_RADIX, ALGO_RADIX2_GLOBAL, ALGO_
 ALGO_NAMES = {"auto": 0, "radix2": 1, "radix4": 2, "split_radix": 3, "radix2_global": 4, "bluestein": 5, "radix2_shfl": 6, "mixed_radix": 7}
 FFT_PREFER_GPU = 1 << 9
 HIP_STREAM_LEGACY = 1  # hipStreamLegacy: the NULL / default stream named explicitly (fft_gpu_plan_set_stream: NULL = the plan's own)
+DCT2, DCT3, DST2, DST3 = range(4)                          # fft_gpu_dct_t
+DCT_NORM_NONE, DCT_NORM_INVERSE, DCT_NORM_ORTHO = range(3)  # fft_gpu_dct_norm_t
+
+
+def _real_prec(dtype):
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("float32 or float64 expected")
+    return PREC_F32 if dt == np.float32 else PREC_F64
 
 
 class PlanInfo(C.Structure):
@@ -81,6 +90,8 @@ SIGNATURES = {
     "fft_gpu_execute_conv2d_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_plan_r2c_2d_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_2d_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_real2d_bins_hip": (_i, [_vp]),
     "fft_gpu_execute_real2d_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_dct_hip": (_vp, [_i, _i, _i, _i, _i]), "fft_gpu_plan_dct_2d_hip": (_vp, [_i, _i, _i, _i, _i, _i]),
+    "fft_gpu_execute_dct_hip": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_host_register_hip": (_i, [_vp, _sz]), "fft_gpu_host_unregister_hip": (_i, [_vp]),
     "fft_gpu_host_is_registered_hip": (_i, [_vp]), "fft_gpu_copy_bench_hip": (C.c_double, [_sz, _i]), "fft_gpu_stream_bench_hip": (C.c_double, [_sz, _i, _i]),
     "fft_gpu_debug_counters_hip": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -117,6 +128,8 @@ SIGNATURES = {
     "fft_gpu_execute_conv2d": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     "fft_gpu_plan_r2c_2d": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_2d": (_vp, [_i, _i, _i, _i]), "fft_gpu_real2d_bins": (_i, [_vp]),
     "fft_gpu_execute_real2d": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
+    "fft_gpu_plan_dct": (_vp, [_i, _i, _i, _i, _i]), "fft_gpu_plan_dct_2d": (_vp, [_i, _i, _i, _i, _i, _i]),
+    "fft_gpu_execute_dct": (_i, [_vp, _vp, C.c_longlong, _vp, C.c_longlong]),
     # include/fft_auto.h
     "fft_plan_dft_1d": (_vp, [_i, _vp, _vp, _i, C.c_uint]), "fft_execute": (None, [_vp]),
     "fft_execute_dft": (None, [_vp, _vp, _vp]), "fft_destroy_plan": (None, [_vp]),
@@ -136,6 +149,7 @@ SIGNATURES = {
     "fft_design_fir_filter_gpu": (_vp, [_i, _i, C.c_double, C.c_double, C.c_double, C.c_double]),
     "fft_convolution_2d_gpu": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]), "fft_filter_2d_gpu": (_i, [_vp, _i, _i, _vp, _vp]),
     "fft_rfft2_gpu": (_i, [_vp, _i, _i, _vp]), "fft_irfft2_gpu": (_i, [_vp, _i, _i, _vp]),
+    "fft_dct_gpu": (_i, [_vp, _i, _i, _i, _vp]), "fft_dct_2d_gpu": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "save_complex_array": (_i, [C.c_char_p, _vp, _i]), "load_complex_array": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_i)]),
     # include/fft_algorithms.h
     "radix2_dit_fft_gpu": (_i, [_vp, _i, _i]), "radix2_fft_gpu": (_i, [_vp, _i, _i]),
@@ -476,6 +490,29 @@ class ExtPlan:
         p.execute = p.execute_real2d
         return p
 
+    @classmethod
+    def dct(cls, n, batch=1, type=DCT2, norm=DCT_NORM_NONE, dtype=np.float64):
+        """DCT / DST plan of type II or III (fft_gpu_plan_dct_hip): batch rows of n reals of dtype float32 / float64, type DCT2 / DCT3 /
+        DST2 / DST3, norm DCT_NORM_NONE / _INVERSE / _ORTHO.  execute(d_in, d_out, in_pitch, out_pitch) runs it on device pointers
+        (pitches in reals between rows, 0: dense; d_in == d_out is allowed)."""
+        p = cls(init().fft_gpu_plan_dct_hip(n, batch, type, norm, _real_prec(dtype)))
+        p.n, p.batch, p.type, p.norm, p.dtype = n, batch, type, norm, np.dtype(dtype)
+        p.execute = p.execute_dct
+        return p
+
+    @classmethod
+    def dct2d(cls, rows, cols, n_matrices=1, type=DCT2, norm=DCT_NORM_NONE, dtype=np.float64):
+        """The same transform along both axes of n_matrices row-major rows x cols real images (fft_gpu_plan_dct_2d_hip).  execute as
+        ExtPlan.dct's, pitches in reals between matrices."""
+        p = cls(init().fft_gpu_plan_dct_2d_hip(rows, cols, n_matrices, type, norm, _real_prec(dtype)))
+        p.rows, p.cols, p.n_matrices, p.type, p.norm, p.dtype = rows, cols, n_matrices, type, norm, np.dtype(dtype)
+        p.execute = p.execute_dct
+        return p
+
+    def execute_dct(self, d_in, d_out, in_pitch=0, out_pitch=0):
+        if self.lib.fft_gpu_execute_dct_hip(self.handle, d_in, in_pitch, d_out, out_pitch) != 0:
+            raise RuntimeError("fft_gpu_execute_dct_hip failed")
+
     def execute_real2d(self, d_in, d_out, in_pitch=0, out_pitch=0):
         if self.lib.fft_gpu_execute_real2d_hip(self.handle, d_in, in_pitch, d_out, out_pitch) != 0:
             raise RuntimeError("fft_gpu_execute_real2d_hip failed")
@@ -741,6 +778,66 @@ def irfft2(X, cols):
     rows = X.shape[-2]
     res = _real2d(np.ascontiguousarray(X).reshape(-1, rows, X.shape[-1]), rows, cols, True)
     return res.reshape(X.shape[:-2] + (rows, cols))
+
+
+def _dct_any(x, kind, type, norm, inverse, two_d, name):
+    """scipy.fft's dct / idct / dst / idst / dctn / idctn for types 2 and 3 on the device.  kind: 0 cosine, 2 sine.  scipy's inverse of
+    type t is the forward transform of the other type, scaled by 1 / (2N) per axis; norm="ortho" scales both the same way."""
+    x = np.asarray(x)
+    if type not in (2, 3):
+        raise NotImplementedError("%s: types 2 and 3 only" % name)
+    if norm not in (None, "backward", "ortho"):
+        raise ValueError("%s: norm None, 'backward' or 'ortho'" % name)
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.float64)) or x.ndim < (2 if two_d else 1) or x.size == 0:
+        raise ValueError("%s takes non-empty float32 or float64 arrays" % name)
+    t = kind + ((3 - type) if inverse else (type - 2))  # DCT2 / DCT3 / DST2 / DST3
+    nm = DCT_NORM_ORTHO if norm == "ortho" else DCT_NORM_INVERSE if inverse else DCT_NORM_NONE
+    a = np.ascontiguousarray(x)
+    if two_d:
+        rows, cols = x.shape[-2:]
+        plan = ExtPlan.dct2d(rows, cols, a.size // (rows * cols), t, nm, x.dtype)
+    else:
+        plan = ExtPlan.dct(x.shape[-1], a.size // x.shape[-1], t, nm, x.dtype)
+    buf = DeviceBuffer(a.nbytes)
+    try:
+        buf.upload(a)
+        plan.execute_dct(buf.ptr, buf.ptr, 0, 0)
+        if plan.sync() != 0:
+            raise RuntimeError("execute failed")
+        return buf.download(x.shape, x.dtype)
+    finally:
+        buf.free()
+        plan.destroy()
+
+
+def dct(x, type=2, norm=None):
+    """scipy.fft.dct over the last axis of a float32 / float64 array, types 2 and 3, on the device (ExtPlan.dct)."""
+    return _dct_any(x, DCT2, type, norm, False, False, "dct")
+
+
+def idct(x, type=2, norm=None):
+    """scipy.fft.idct over the last axis: idct(dct(x, type), type) = x."""
+    return _dct_any(x, DCT2, type, norm, True, False, "idct")
+
+
+def dst(x, type=2, norm=None):
+    """scipy.fft.dst over the last axis, types 2 and 3."""
+    return _dct_any(x, DST2, type, norm, False, False, "dst")
+
+
+def idst(x, type=2, norm=None):
+    """scipy.fft.idst over the last axis."""
+    return _dct_any(x, DST2, type, norm, True, False, "idst")
+
+
+def dctn(x, type=2, norm=None):
+    """scipy.fft.dctn over the last two axes (ExtPlan.dct2d)."""
+    return _dct_any(x, DCT2, type, norm, False, True, "dctn")
+
+
+def idctn(x, type=2, norm=None):
+    """scipy.fft.idctn over the last two axes."""
+    return _dct_any(x, DCT2, type, norm, True, True, "idctn")
 
 
 def filter2d(x, H):

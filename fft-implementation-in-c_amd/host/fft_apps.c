@@ -363,3 +363,30 @@ int fft_irfft2_gpu(const complex_t* spec, int rows, int cols, double* image) {
     const size_t nr = (size_t)rows * (size_t)cols, ns = (size_t)rows * (size_t)(cols / 2 + 1);
     return run_real2d(spec, ns * sizeof(complex_t), image, nr * sizeof(double), rows, cols, 0);
 }
+
+/* one DCT / DST plan (rows = 0: 1D of length cols) on host arrays of doubles, in place in one device buffer */
+static int run_dct(const double* in, double* out, int rows, int cols, int type, int norm) {
+    if (!in || !out || cols <= 0 || rows < 0 || type < 0 || type > 3 || norm < 0 || norm > 2 || (long long)(rows ? rows : 1) * cols > (1ll << 30)) return -1;
+    if (ensure_gpu() != 0) return -1;
+    int rc = -1;
+    const size_t bytes = (size_t)(rows ? rows : 1) * (size_t)cols * sizeof(double);
+    fft_gpu_plan_t plan = rows ? fft_gpu_plan_dct_2d_hip(rows, cols, 1, (fft_gpu_dct_t)type, (fft_gpu_dct_norm_t)norm, FFT_PREC_F64)
+                               : fft_gpu_plan_dct_hip(cols, 1, (fft_gpu_dct_t)type, (fft_gpu_dct_norm_t)norm, FFT_PREC_F64);
+    fft_gpu_memory_t buf = plan ? fft_gpu_alloc_bytes_hip(bytes) : NULL;
+    if (plan && buf) {
+        if (fft_gpu_copy_h2d_bytes_hip(buf, in, bytes) == 0 &&
+            fft_gpu_execute_dct_hip(plan, fft_gpu_memory_ptr(buf), 0, fft_gpu_memory_ptr(buf), 0) == 0 && fft_gpu_plan_sync(plan) == 0 &&
+            fft_gpu_copy_d2h_bytes_hip(out, buf, bytes) == 0)
+            rc = 0;
+    }
+    fft_gpu_free(buf);
+    fft_gpu_destroy_plan(plan);
+    return rc;
+}
+
+int fft_dct_gpu(const double* x, int n, int type, int norm, double* out) { return run_dct(x, out, 0, n, type, norm); }
+
+int fft_dct_2d_gpu(const double* image, int rows, int cols, int type, int norm, double* out) {
+    if (rows <= 0) return -1;
+    return run_dct(image, out, rows, cols, type, norm);
+}

@@ -297,6 +297,22 @@ int fft_gpu_execute_real2d(fft_gpu_plan_t plan, const void* d_in, long long in_p
     return fft_gpu_execute_real2d_hip(plan, d_in, in_pitch, d_out, out_pitch);
 }
 
+/* DCT / DST plans of types II and III (fft_hip.h) */
+fft_gpu_plan_t fft_gpu_plan_dct(int n, int batch, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_dct")) return NULL;
+    return fft_gpu_plan_dct_hip(n, batch, type, norm, prec);
+}
+
+fft_gpu_plan_t fft_gpu_plan_dct_2d(int rows, int cols, int n_matrices, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec) {
+    if (!backend_is_hip("fft_gpu_plan_dct_2d")) return NULL;
+    return fft_gpu_plan_dct_2d_hip(rows, cols, n_matrices, type, norm, prec);
+}
+
+int fft_gpu_execute_dct(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch) {
+    if (!backend_is_hip("fft_gpu_execute_dct")) return -1;
+    return fft_gpu_execute_dct_hip(plan, d_in, in_pitch, d_out, out_pitch);
+}
+
 int fft_gpu_device_count(void) { return fft_gpu_device_count_hip(); }
 
 /* a stub in the reference (gpu/fft_gpu.c:359-363); real here: later allocations and plans go to `device` */

@@ -76,6 +76,11 @@ int fft_filter_2d_gpu(const complex_t* image, int rows, int cols, const complex_
  * (fft_gpu_plan_r2c_2d_hip / fft_gpu_plan_c2r_2d_hip).  0 / -1, -1 without a device. */
 int fft_rfft2_gpu(const double* image, int rows, int cols, complex_t* out);
 int fft_irfft2_gpu(const complex_t* spec, int rows, int cols, double* image);
+/* Cosine / sine transform of n doubles, and of a row-major rows x cols image along both axes (the transform behind image compression that
+ * applications/image_fft.c points at): type = fft_gpu_dct_t (DCT-II, DCT-III, DST-II, DST-III), norm = fft_gpu_dct_norm_t, scipy.fft's
+ * conventions (fft_hip.h).  Host pointers; ONE plan each (fft_gpu_plan_dct_hip / fft_gpu_plan_dct_2d_hip).  0 / -1, -1 without a device. */
+int fft_dct_gpu(const double* x, int n, int type, int norm, double* out);
+int fft_dct_2d_gpu(const double* image, int rows, int cols, int type, int norm, double* out);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,10 @@ fft_gpu_plan_t fft_gpu_plan_r2c_2d(int rows, int cols, int n_matrices, fft_preci
 fft_gpu_plan_t fft_gpu_plan_c2r_2d(int rows, int cols, int n_matrices, fft_precision_t prec);
 int fft_gpu_real2d_bins(fft_gpu_plan_t plan);
 int fft_gpu_execute_real2d(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
+/* DCT / DST plans of types II and III (fft_gpu_plan_dct_hip, fft_hip.h) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_dct(int n, int batch, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
+fft_gpu_plan_t fft_gpu_plan_dct_2d(int rows, int cols, int n_matrices, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
+int fft_gpu_execute_dct(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
 #ifdef __cplusplus
 }
 #endif

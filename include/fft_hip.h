@@ -352,6 +352,27 @@ int fft_gpu_real2d_bins_hip(fft_gpu_plan_t plan);  /* cols/2 + 1; -1: not such a
  * complex values); the rows of a matrix are dense; the elements between matrices are neither read nor written, and the input never is
  * written.  -1, nothing launched: NULL pointers, a plan of another kind, a pitch smaller than its matrix, d_out overlapping d_in. */
 int fft_gpu_execute_real2d_hip(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
+/* Cosine and sine transforms of types II and III of batched real rows, scipy.fft's conventions (the reference's applications/image_fft.c
+ * names the DCT as the transform behind image compression and has none):
+ *   DCT-II   X[k] = 2 sum_n x[n] cos(pi k (2n+1) / 2N)        DCT-III  y[n] = X[0] + 2 sum_{k>=1} X[k] cos(pi k (2n+1) / 2N)
+ *   DST-II   X[k] = 2 sum_n x[n] sin(pi (k+1)(2n+1) / 2N)     DST-III  y[n] = (-1)^n X[N-1] + 2 sum_{k<N-1} X[k] sin(pi (2n+1)(k+1) / 2N)
+ * NORM_NONE: as above (scipy's norm=None).  NORM_INVERSE: times 1 / (2N), what scipy's idct / idst of the OTHER type apply: idct(X, type=2)
+ * is DCT3 with NORM_INVERSE.  NORM_ORTHO: scipy's norm="ortho".  Where N is a power of two, 16 <= N <= 8192 in fp32 and 8 <= N <= 4096 in
+ * fp64 on the MI355X, an execute is ONE launch that reads and writes every row once (Makhoul's algorithm on a half-length complex transform
+ * inside the kernel); every other N >= 1, and FFT_GPU_OPT_NO_FUSION: a permute kernel, a length-N complex plan in a workspace of the plan's
+ * own, a twiddle kernel.  fft_gpu_plan_info_hip: n = N, batch, the passes and factors of that core, fused = 1 / 0.
+ * NULL: non-positive sizes, an unknown type or norm, n * batch > 2^31 - 1, a failed allocation. */
+typedef enum { FFT_GPU_DCT2 = 0, FFT_GPU_DCT3 = 1, FFT_GPU_DST2 = 2, FFT_GPU_DST3 = 3 } fft_gpu_dct_t;
+typedef enum { FFT_GPU_DCT_NORM_NONE = 0, FFT_GPU_DCT_NORM_INVERSE = 1, FFT_GPU_DCT_NORM_ORTHO = 2 } fft_gpu_dct_norm_t;
+fft_gpu_plan_t fft_gpu_plan_dct_hip(int n, int batch, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
+/* the same type and norm along both axes of n_matrices row-major rows x cols real images: scipy's dctn / idctn over the last two axes.
+ * A composition: the row plan, a real transpose, the row plan of length rows, a transpose back; fused = 1 where both row plans are.
+ * NULL also: rows * cols > 2^30 or rows * cols * n_matrices > 2^31 - 1. */
+fft_gpu_plan_t fft_gpu_plan_dct_2d_hip(int rows, int cols, int n_matrices, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
+/* async on the plan's stream.  Pitches count reals between rows (1D plans) or between matrices (2D plans, whose rows are dense); 0: dense.
+ * Any sizeof(real)-aligned base and any pitch work; 16-byte aligned bases and pitches get 16-byte accesses.  d_in == d_out with equal
+ * pitches is allowed.  -1, nothing launched: a NULL plan or pointer, a plan of another kind, a pitch smaller than the row or matrix. */
+int fft_gpu_execute_dct_hip(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
 int fft_gpu_plan_info_hip(fft_gpu_plan_t plan, fft_gpu_plan_info_t* info);
 /* NULL = the plan's own (non-blocking) stream.  A caller that works on HIP's default stream -- PyTorch's default stream
  * has the handle 0 -- names it explicitly: (void*)1 = hipStreamLegacy, or its work and the plan's are not ordered. */
