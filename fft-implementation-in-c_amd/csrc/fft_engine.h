@@ -76,9 +76,13 @@ struct EnginePolicy {
 
 // Element-wise work fused into the first pass's load and the last pass's store of one execute (fftk::TileHooks).
 // Pitches are in elements; 0 = the plan's n.  Tables live in device memory; pre_tab must be readable up to the next
-// multiple of 16 bytes past n_in (the planner pads its own tables).
+// multiple of 16 bytes past n_in (the planner pads its own tables).  The entry point says which kernel variant runs
+// (fft_rows_list.h); the fields are data, read by the entry points their group names and ignored by the others.
 template <typename T>
 struct ExecHooks {
+    // ends: execute_hooked, _chain, _round, _frames (there in_pitch = the hop).  execute_iframes: pre_tab = W_2n^k (k <= n, shared) is the
+    // c2r merge's table, not a factor, and the row pitch in is n + 1 whatever in_pitch says.  execute_filter: in_pitch = B, the block
+    // advance; no tables, whole blocks
     const fftk::cpx<T>* pre_tab = nullptr;
     int pre_mode = fftk::HOOK_NONE;
     long long n_in = 0;        // valid input samples per transform (0: n); the rest reads as zero
@@ -88,29 +92,23 @@ struct ExecHooks {
     int post_mode = fftk::HOOK_NONE;
     long long n_out = 0;       // outputs stored per transform (0: n)
     long long out_pitch = 0;
-    // single-pass plans only (execute_round): the spectral product between the forward and the inverse transform of ONE kernel
+    // mid: execute_round, execute_filter -- the spectral product between the forward and the inverse transform of ONE kernel
     const fftk::cpx<T>* mid_tab = nullptr;
     int mid_mode = fftk::HOOK_NONE;
-    // single-pass plans only (execute_frames): the transforms of the execute are overlapping FRAMES of signals, frame f at
-    // in + (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_pitch (in_pitch = the hop); 0: plain rows.
-    // power_out: not NULL = the store side writes one-sided power rows of n/2 + 1 reals there, scaled by power_scale.
+    // frame split: execute_frames, execute_filter -- the transforms of the execute are overlapping FRAMES (blocks) of signals, frame f
+    // at in + (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_pitch; frames_per_signal >= 1
     int frames_per_signal = 0;
     long long signal_pitch = 0;
+    // frame rows: execute_frames -- power_out not NULL: one-sided power rows of n/2 + 1 reals go there, scaled by power_scale, instead
+    // of complex rows.  real_frames: `in` holds REAL samples (in_pitch and signal_pitch count reals), the plan's n is HALF the frame
+    // length, pre_tab the window packed in pairs (HOOK_MUL_PAIR), post_tab = W_2n^k (k < n, shared), and n + 1 one-sided bins leave:
+    // complex at out_pitch = n + 1, or power rows of n + 1 reals (TileHooks, HOOKBIT_REAL)
     T* power_out = nullptr;
     T power_scale = (T)1;
-    // execute_frames only: `in` holds REAL samples (in_pitch = the hop and signal_pitch count reals), the plan's n is HALF the frame
-    // length, pre_tab the window packed in pairs (HOOK_MUL_PAIR), post_tab = W_2n^k (k < n, shared), and the rows that leave are the
-    // n + 1 one-sided bins of the real transform: complex at out_pitch = n + 1, or power rows of n + 1 reals (TileHooks, HOOK bit 6)
     bool real_frames = false;
-    // single-pass plans only (execute_iframes): `in` holds one-sided rows of n + 1 bins of real transforms of length 2 n, row f at
-    // in + f * (n + 1); pre_tab = W_2n^k (k <= n, shared) is the c2r merge's table, and the rows that leave are the frames' 2 n real
-    // samples read as n complex values (TileHooks, HOOK bit 7)
-    bool herm_rows = false;
-    // single-pass plans only (execute_filter): overlap-save filtering.  The transforms of the execute are the blocks of signals, block
-    // w of a signal starting frame_lead samples before its sample w * in_pitch (in_pitch = B, the block advance); samples outside
-    // [0, signal_len) read as zero.  mid_tab = the filter's spectrum; of every block's result the values l >= frame_lead go to
-    // out + sig * out_signal_pitch + (w * B + l - frame_lead - out_off), inside [0, out_len) only (TileHooks, HOOK bits 8 and 9)
-    bool filter = false;
+    // filter geometry: execute_filter -- block w of a signal starts frame_lead samples before its sample w * in_pitch; samples outside
+    // [0, signal_len) read as zero; of every block's result the values l >= frame_lead go to
+    // out + sig * out_signal_pitch + (w * in_pitch + l - frame_lead - out_off), inside [0, out_len) only (TileHooks, HOOKBIT_BOUND, _VALID)
     int frame_lead = 0;
     long long signal_len = 0;
     long long out_signal_pitch = 0;
@@ -1237,8 +1235,8 @@ class Pow2Plan {
         }
     }
 
-    // ---- fused element-wise work (fftk::TileHooks): three HOOK instantiations cover AUTO's plans -- the single-pass
-    // rows kernel, the first (column) pass and the last (transposing row) pass
+    // ---- fused element-wise work (fftk::TileHooks): hooked kernels cover AUTO's plans -- 1 the single-pass rows kernel (its variants:
+    // FFT_ROWS_HOOK_LIST, fft_rows_list.h), 2 / 4 the first (column) pass, 3 the last (transposing row) pass
     static int hook_kind(const PassDesc& p) {
         using namespace fftk;
         if (p.log2H != 0) return 0;
@@ -1262,7 +1260,7 @@ class Pow2Plan {
         using namespace fftk;
         static const int use_fixed = FFT_EXP_ENV("FFT_HIP_FIXED") ? atoi(FFT_EXP_ENV("FFT_HIP_FIXED")) : 1;
         // (the fp64 store-hooked row pass spills 23...42 VGPRs with its shape baked in: generic there)
-        constexpr bool FIX_OK = !(SZ == 16 && (HOOK & 2));
+        constexpr bool FIX_OK = !(SZ == 16 && (HOOK & HOOKBIT_STORE));
         if constexpr (FIX_OK) {
             if (use_fixed && is_full_tile(p.log2L, p.log2C) &&
                 with_constant<7, 10>(p.log2L, [&](auto l) { launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, full_tile_fix(decltype(l)::value), HOOK>, tp, -1, p); }))
@@ -1271,23 +1269,24 @@ class Pow2Plan {
         launch_kernel(tile_fft_kernel<T, 8, 1, FAM, LM, SM, TW, 0, HOOK>, tp, -1, p);
     }
 
-    // side: bit 0 this launch carries the load side of `h`, bit 1 the store side
-    void launch_pass_hooked(size_t ipass, const cpx<T>* in, cpx<T>* out, int nb, bool inverse, T scale, const ExecHooks<T>& h, int side,
-                            long long tab_off) {
+    // pass_params with the ends of `h` filled in.  side: HOOKBIT_LOAD this launch carries the load side of `h`, HOOKBIT_STORE the store
+    // side.  This is all a pass of a multi-pass plan and the PLAIN rows variant need; the other variants add their fillers below.
+    fftk::TileParams<T> hooked_params(size_t ipass, const cpx<T>* in, cpx<T>* out, int nb, bool inverse, T scale, const ExecHooks<T>& h, int side,
+                                      long long tab_off) {
         using namespace fftk;
         const PassDesc& p = passes[ipass];
         TileParams<T> tp = pass_params(ipass, in, out, nb, inverse, scale);
         const long long n = 1ll << log2n;
         TileHooks<T>& k = tp.hk;
         k.n_in = 0x7fffffff; k.n_out = 0x7fffffff; k.in_vec_ok = 1; k.out_vec_ok = 1;
-        if (side & 1) {
+        if (side & HOOKBIT_LOAD) {
             const long long pitch = h.in_pitch ? h.in_pitch : n;
             k.pre_tab = h.pre_tab; k.pre_mode = h.pre_tab ? h.pre_mode : HOOK_NONE;
             k.n_in = (int)(h.n_in ? h.n_in : n);
             k.in_vec_ok = (pitch % V) == 0 ? 1 : 0;
             if (p.n_cols < 0) tp.in_c = pitch; else tp.in_b = pitch;
         }
-        if (side & 2) {
+        if (side & HOOKBIT_STORE) {
             const long long pitch = h.out_pitch ? h.out_pitch : n;
             k.post_tab = h.post_tab ? h.post_tab + tab_off : nullptr;
             k.post_tab_b = h.post_tab_b;
@@ -1296,100 +1295,114 @@ class Pow2Plan {
             k.out_vec_ok = (pitch % V) == 0 ? 1 : 0;
             if (p.n_cols < 0) tp.out_c = pitch; else tp.out_b = pitch;
         }
-        if (side & 4) {  // FFT -> mid product -> inverse FFT in this one launch (single-pass plans: execute_round)
-            k.mid_tab = h.mid_tab;
-            k.mid_mode = (h.mid_tab || h.mid_mode == HOOK_ABS2) ? h.mid_mode : HOOK_NONE;
-            if (h.filter) {  // overlap-save blocks (execute_filter): bounded framed load, round trip, valid-part framed store
-                if (hook_kind(p) != 1 || side != (3 | 4) || h.frames_per_signal < 1) return;
-                k.pre_tab = nullptr; k.pre_mode = HOOK_NONE;
-                k.post_tab = nullptr; k.post_mode = HOOK_NONE;
-                k.n_in = (int)n; k.n_out = (int)n;
-                k.frames_per_signal = h.frames_per_signal;
-                k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
-                k.signal_pitch = h.signal_pitch;
-                k.frame_lead = h.frame_lead;
-                k.signal_len = (int)h.signal_len;
-                k.out_signal_pitch = h.out_signal_pitch;
-                k.out_len = (int)h.out_len;
-                k.out_off = (int)h.out_off;
-                // base and pitch aligned; the kernel decides chunk by chunk from the sample position
-                k.in_vec_ok = ((h.signal_pitch % V) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
-                k.out_vec_ok = ((h.out_signal_pitch % V) == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-                tp.nt &= ~1;  // blocks always overlap: their lines are asked for again
-                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, FFT_ROWS_FILTER_HOOK>, tp, -1, p);
-                return;
-            }
-            if (hook_kind(p) == 1) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 8>, tp, -1, p);
-            return;
+        return tp;
+    }
+    // FFT -> mid product -> inverse FFT in one launch (ROUND, FILTER)
+    static void fill_mid(fftk::TileHooks<T>& k, const ExecHooks<T>& h) {
+        k.mid_tab = h.mid_tab;
+        k.mid_mode = (h.mid_tab || h.mid_mode == fftk::HOOK_ABS2) ? h.mid_mode : fftk::HOOK_NONE;
+    }
+    // the frame -> (signal, frame in signal) split (the FRAMES variants, FILTER): one multiply-high by ceil(2^32 / d) in the kernel,
+    // exact while f * d < 2^32 for every tile column f, the padding columns of the last tile included (frames_exact)
+    static void fill_frame_split(fftk::TileHooks<T>& k, const ExecHooks<T>& h) {
+        k.frames_per_signal = h.frames_per_signal;
+        k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
+        k.signal_pitch = h.signal_pitch;
+    }
+    // overlapping frames (FRAMES, FRAMES_POWER; RFRAMES, RFRAMES_POWER).  reals: scalars of `in` per complex sample of a frame -- 1: complex
+    // signals; 2: real signals, where the hop, the signal pitch and the frame length (2 n) count REAL samples, 16 / sizeof(T) = 2 V of
+    // them per 16 bytes
+    void fill_frames(fftk::TileParams<T>& tp, const ExecHooks<T>& h, const cpx<T>* in, const cpx<T>* out, int reals) {
+        fftk::TileHooks<T>& k = tp.hk;
+        const long long n = 1ll << log2n;
+        const long long hop = h.in_pitch ? h.in_pitch : reals * n;
+        fill_frame_split(k, h);
+        // 16-byte loads only where EVERY frame starts 16-byte aligned: the base, the hop and the signal pitch
+        k.in_vec_ok = ((hop % (reals * V)) == 0 && (h.signal_pitch % (reals * V)) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+        if (((uintptr_t)out & 15) != 0) k.out_vec_ok = 0;
+        // a sample belongs to n / hop frames: the loads of overlapping frames carry no non-temporal hint (their lines are asked for again)
+        if (hop < reals * n) tp.nt &= ~1;
+        k.power_out = h.power_out;
+        k.power_scale = h.power_scale;
+    }
+    // one-sided rows in (HERM_ROWS)
+    void fill_herm_rows(fftk::TileParams<T>& tp, const cpx<T>* in) {
+        fftk::TileHooks<T>& k = tp.hk;
+        const long long n = 1ll << log2n;
+        k.pre_mode = fftk::HOOK_NONE;  // pre_tab is the merge's table, not a factor
+        k.n_in = (int)n;
+        tp.in_c = n + 1;
+        // rows of n + 1 bins: 16-byte aligned only where a bin is 16 bytes (fp64) and the base is
+        k.in_vec_ok = (V == 1 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+    }
+    // overlap-save blocks (FILTER): bounded framed load, round trip, valid-part framed store
+    void fill_filter(fftk::TileParams<T>& tp, const ExecHooks<T>& h, const cpx<T>* in, const cpx<T>* out) {
+        fftk::TileHooks<T>& k = tp.hk;
+        const long long n = 1ll << log2n;
+        fill_mid(k, h);
+        fill_frame_split(k, h);
+        k.pre_tab = nullptr; k.pre_mode = fftk::HOOK_NONE;
+        k.post_tab = nullptr; k.post_mode = fftk::HOOK_NONE;
+        k.n_in = (int)n; k.n_out = (int)n;
+        k.frame_lead = h.frame_lead;
+        k.signal_len = (int)h.signal_len;
+        k.out_signal_pitch = h.out_signal_pitch;
+        k.out_len = (int)h.out_len;
+        k.out_off = (int)h.out_off;
+        // base and pitch aligned; the kernel decides chunk by chunk from the sample position
+        k.in_vec_ok = ((h.signal_pitch % V) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
+        k.out_vec_ok = ((h.out_signal_pitch % V) == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+        tp.nt &= ~1;  // blocks always overlap: their lines are asked for again
+    }
+
+    // the hooked single-pass rows kernel: FFT_ROWS_HOOK_LIST (fft_rows_list.h) as a switch, and the only place that names it.  The
+    // caller has checked round_capable(): the plan's one pass is that kernel's shape.
+    void launch_rows_hooked(fftk::RowsHook variant, const fftk::TileParams<T>& tp, const PassDesc& p) {
+        using namespace fftk;
+        switch (variant) {
+#define FFT_ROWS_HOOK_CASE(NAME, bits) \
+    case ROWS_HOOK_##NAME: launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, (bits)>, tp, -1, p); break;
+            FFT_ROWS_HOOK_LIST(FFT_ROWS_HOOK_CASE)
+#undef FFT_ROWS_HOOK_CASE
         }
-        if (h.herm_rows) {  // one-sided rows in (execute_iframes): the hooked single-pass rows kernel with its Hermitian rows load
-            if (hook_kind(p) != 1 || side != 3) return;
-            k.pre_tab = h.pre_tab; k.pre_mode = HOOK_NONE;  // the merge's table, not a factor
-            k.n_in = (int)n;
-            tp.in_c = n + 1;
-            // rows of n + 1 bins: 16-byte aligned only where a bin is 16 bytes (fp64) and the base is
-            k.in_vec_ok = (V == 1 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
-            launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 1 | 128>, tp, -1, p);
-            return;
-        }
-        if (h.frames_per_signal > 0) {  // overlapping frames (execute_frames): the hooked single-pass rows kernel with its framed load
-            if (hook_kind(p) != 1 || side != 3) return;
-            const long long hop = h.in_pitch ? h.in_pitch : (h.real_frames ? 2 * n : n);
-            k.frames_per_signal = h.frames_per_signal;
-            k.frames_rcp = h.frames_per_signal > 1 ? (unsigned)(((1ull << 32) + (unsigned)h.frames_per_signal - 1) / (unsigned)h.frames_per_signal) : 0u;
-            k.signal_pitch = h.signal_pitch;
-            // 16-byte loads only where EVERY frame starts 16-byte aligned: the base, the hop and the signal pitch
-            k.in_vec_ok = ((hop % V) == 0 && (h.signal_pitch % V) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
-            if (((uintptr_t)out & 15) != 0) k.out_vec_ok = 0;
-            // a sample belongs to n / hop frames: the loads of overlapping frames carry no non-temporal hint (their lines are asked for again)
-            if (hop < n) tp.nt &= ~1;
-            if (h.real_frames) {  // hop, pitch and frame length (2 n) in REAL samples, 16 / sizeof(T) = 2 V of them per 16 bytes
-                k.in_vec_ok = ((hop % (2 * V)) == 0 && (h.signal_pitch % (2 * V)) == 0 && ((uintptr_t)in & 15) == 0) ? 1 : 0;
-                if (hop < 2 * n) tp.nt &= ~1;
-                k.power_out = h.power_out;
-                k.power_scale = h.power_scale;
-                if (h.power_out) launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 32 | 64>, tp, -1, p);
-                else launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 64>, tp, -1, p);
-                return;
-            }
-            if (h.power_out) {
-                k.power_out = h.power_out;
-                k.power_scale = h.power_scale;
-                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16 | 32>, tp, -1, p);
-            } else {
-                launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3 | 16>, tp, -1, p);
-            }
-            return;
-        }
+    }
+    // a pass of a multi-pass plan with one end of `h`: the first (column) pass with its load side, the last (transposing row) pass
+    // with its store side
+    void launch_pass_hooked(size_t ipass, const cpx<T>* in, cpx<T>* out, int nb, bool inverse, T scale, const ExecHooks<T>& h, int side,
+                            long long tab_off) {
+        using namespace fftk;
+        const PassDesc& p = passes[ipass];
+        const TileParams<T> tp = hooked_params(ipass, in, out, nb, inverse, scale, h, side, tab_off);
         switch (hook_kind(p)) {
-            // HOOK bits: 1 load side, 2 store side, 4 table values prefetched with the data, 8 round trip, 16 framed load, 32 one-sided
-            // power store, 64 real frames, 128 Hermitian rows load (fft_kernels.h)
-            case 1: launch_kernel(tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, 3>, tp, -1, p); break;
-            case 2: launch_kernel(tile_fft_kernel<T, 8, 1, FAM_R4, LOAD_CCONTIG, STORE_CCONTIG, true, 0, 1 | 4>, tp, -1, p); break;
-            case 3: launch_hooked_fixed<FAM_SR16, LOAD_LCONTIG, STORE_CCONTIG, false, 2>(tp, p); break;
-            case 4: launch_hooked_fixed<FAM_SR16, LOAD_CCONTIG, STORE_CCONTIG, true, 1 | 4>(tp, p); break;
+            case 2: launch_kernel(tile_fft_kernel<T, 8, 1, FAM_R4, LOAD_CCONTIG, STORE_CCONTIG, true, 0, HOOKBIT_LOAD | HOOKBIT_TABPF>, tp, -1, p); break;
+            case 3: launch_hooked_fixed<FAM_SR16, LOAD_LCONTIG, STORE_CCONTIG, false, HOOKBIT_STORE>(tp, p); break;
+            case 4: launch_hooked_fixed<FAM_SR16, LOAD_CCONTIG, STORE_CCONTIG, true, HOOKBIT_LOAD | HOOKBIT_TABPF>(tp, p); break;
             default: break;
         }
     }
 
-    // ---- single-pass sizes: out = IFFT( mid( FFT( pre(in) ) ) ) * post as ONE kernel (TileHooks::mid_tab): the transform pair
-    // of a small Bluestein or convolution costs one HBM round trip of the user's data, nothing else.  The mid table is shared
-    // by the batch (h.mid_tab) or absent (HOOK_ABS2); per-transform products (cross-correlation) take two kernels.
+    // ---- single-pass sizes.  Each entry point below requires round_capable() -- the plan is ONE pass of the hooked rows kernel's
+    // shape -- and launches nothing without it; it picks its variant of that kernel and adds the variant's filler to the common ends.
     bool round_capable() const { return hook_capable() && passes.size() == 1 && hook_kind(passes[0]) == 1; }
+    static constexpr int kBothEnds = fftk::HOOKBIT_LOAD | fftk::HOOKBIT_STORE;
+
+    // out = IFFT( mid( FFT( pre(in) ) ) ) * post as ONE kernel (TileHooks::mid_tab): the transform pair of a small Bluestein or
+    // convolution costs one HBM round trip of the user's data, nothing else.  The mid table is shared by the batch (h.mid_tab) or
+    // absent (HOOK_ABS2); per-transform products (cross-correlation) take two kernels.
     void execute_round(const cpx<T>* in, cpx<T>* out, int nb, const ExecHooks<T>& h, T extra_scale = (T)1) {
         const long long n = 1ll << log2n;
         const T scale = (T)((1.0L / (long double)n) * (long double)extra_scale);
         run_if = nullptr;
-        launch_pass_hooked(0, in, out, nb, false, scale, h, 3 | 4, 0);
+        if (!round_capable()) return;
+        fftk::TileParams<T> tp = hooked_params(0, in, out, nb, false, scale, h, kBothEnds, 0);
+        fill_mid(tp.hk, h);
+        launch_rows_hooked(fftk::ROWS_HOOK_ROUND, tp, passes[0]);
         rt->mark(0);
     }
 
-    // ---- single-pass sizes: the nf transforms of one launch are overlapping frames of signals (ExecHooks::frames_per_signal,
-    // signal_pitch; in_pitch = the hop), windowed by h.pre_tab on the way in; the results leave as complex rows of n bins (out) or,
-    // with h.power_out, as one-sided power rows.  h.real_frames: the signals are real, a frame is 2 n reals and n + 1 bins leave.
-    // Requires round_capable() and frames_exact(nf, frames_per_signal).
-    // The frame -> (signal, frame in signal) split in the kernel is one multiply-high by ceil(2^32 / d): exact while f * d < 2^32
-    // for every tile column f, the padding columns of the last tile included.
+    // the nf transforms of one launch are overlapping frames of signals (ExecHooks' frame split; in_pitch = the hop), windowed by
+    // h.pre_tab on the way in; the results leave as complex rows of n bins (out) or, with h.power_out, as one-sided power rows.
+    // h.real_frames: the signals are real, a frame is 2 n reals and n + 1 bins leave.  Requires frames_exact(nf, frames_per_signal).
     bool frames_exact(long long nf, int frames_per_signal) const {
         if (passes.empty() || nf < 1 || nf > 0x7fffffff) return false;
         const long long C = 1ll << passes[0].log2C;
@@ -1397,28 +1410,39 @@ class Pow2Plan {
         return cols * (long long)frames_per_signal <= (1ll << 32);
     }
     void execute_frames(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
+        using namespace fftk;
         run_if = nullptr;
-        launch_pass_hooked(0, in, out, nf, false, (T)1, h, 3, 0);
+        if (!round_capable() || h.frames_per_signal < 1) return;
+        TileParams<T> tp = hooked_params(0, in, out, nf, false, (T)1, h, kBothEnds, 0);
+        fill_frames(tp, h, in, out, h.real_frames ? 2 : 1);
+        launch_rows_hooked(h.real_frames ? (h.power_out ? ROWS_HOOK_RFRAMES_POWER : ROWS_HOOK_RFRAMES) : (h.power_out ? ROWS_HOOK_FRAMES_POWER : ROWS_HOOK_FRAMES), tp,
+                           passes[0]);
         rt->mark(0);
     }
 
-    // ---- single-pass sizes: overlap-save filtering (ExecHooks::filter) -- the nf transforms of ONE launch are the overlapping blocks of
-    // signals, multiplied by h.mid_tab between the forward and the inverse transform, and only the valid part of every block is
-    // stored, straight into the output signals.  Requires round_capable() and frames_exact(nf, frames_per_signal).
+    // overlap-save filtering: the nf transforms of ONE launch are the overlapping blocks of signals (ExecHooks' frame split and filter
+    // geometry), multiplied by h.mid_tab between the forward and the inverse transform, and only the valid part of every block is
+    // stored, straight into the output signals.  Requires frames_exact(nf, frames_per_signal).
     void execute_filter(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
         const long long n = 1ll << log2n;
         run_if = nullptr;
-        launch_pass_hooked(0, in, out, nf, false, (T)(1.0L / (long double)n), h, 3 | 4, 0);
+        if (!round_capable() || h.frames_per_signal < 1) return;
+        fftk::TileParams<T> tp = hooked_params(0, in, out, nf, false, (T)(1.0L / (long double)n), h, kBothEnds, 0);
+        fill_filter(tp, h, in, out);
+        launch_rows_hooked(fftk::ROWS_HOOK_FILTER, tp, passes[0]);
         rt->mark(0);
     }
 
-    // ---- single-pass sizes: the nf rows of one launch are one-sided spectra of n + 1 bins (h.herm_rows, h.pre_tab = W_2n^k); the
-    // c2r merge rides on the load, the inverse transform is scaled by 1 / n, and out takes nf rows of n complex values -- the 2 n
-    // real samples of every frame, 1 / (2 n)-scaled like every inverse of the library.  Requires round_capable().
+    // the nf rows of one launch are one-sided spectra of n + 1 bins (h.pre_tab = W_2n^k); the c2r merge rides on the load, the inverse
+    // transform is scaled by 1 / n, and out takes nf rows of n complex values -- the 2 n real samples of every frame, 1 / (2 n)-scaled
+    // like every inverse of the library.
     void execute_iframes(const cpx<T>* in, cpx<T>* out, int nf, const ExecHooks<T>& h) {
         const long long n = 1ll << log2n;
         run_if = nullptr;
-        launch_pass_hooked(0, in, out, nf, true, (T)(1.0L / (long double)n), h, 3, 0);
+        if (!round_capable()) return;
+        fftk::TileParams<T> tp = hooked_params(0, in, out, nf, true, (T)(1.0L / (long double)n), h, kBothEnds, 0);
+        fill_herm_rows(tp, in);
+        launch_rows_hooked(fftk::ROWS_HOOK_HERM_ROWS, tp, passes[0]);
         rt->mark(0);
     }
 
@@ -1485,14 +1509,14 @@ class Pow2Plan {
         run_if = nullptr;
         for (int b0 = 0; b0 < nb; b0 += chunk) {
             const int cb = (nb - b0) < chunk ? (nb - b0) : chunk;
-            launch_pass_hooked(0, in + (size_t)b0 * (size_t)ip, scratch, cb, false, (T)1, hf, 1, 0);
+            launch_pass_hooked(0, in + (size_t)b0 * (size_t)ip, scratch, cb, false, (T)1, hf, fftk::HOOKBIT_LOAD, 0);
             rt->mark(0);
             if (passes.size() == 3) launch_pass(1, scratch, scratch, cb, false, (T)1);
             launch_chain(scratch, scratch2, cb, hf, (long long)b0 * hf.post_tab_b);
             rt->mark(1);
             if (passes.size() == 3) launch_pass(1, scratch2, scratch2, cb, true, (T)1);
             inv_plan()->run_if = nullptr;
-            inv_plan()->launch_pass_hooked(last, scratch2, out + (size_t)b0 * (size_t)op, cb, true, scale, hi, 2, (long long)b0 * hi.post_tab_b);
+            inv_plan()->launch_pass_hooked(last, scratch2, out + (size_t)b0 * (size_t)op, cb, true, scale, hi, fftk::HOOKBIT_STORE, (long long)b0 * hi.post_tab_b);
             rt->mark(2);
         }
         return true;
@@ -1504,8 +1528,9 @@ class Pow2Plan {
         const T scale = (T)((inverse ? 1.0L / (long double)n : 1.0L) * (long double)extra_scale);
         const long long ip = h.in_pitch ? h.in_pitch : n, op = h.out_pitch ? h.out_pitch : n;
         run_if = nullptr;
-        if (passes.size() == 1) {
-            launch_pass_hooked(0, in, out, nb, inverse, scale, h, 3, 0);
+        if (passes.size() == 1) {  // the PLAIN variant of the hooked rows kernel
+            if (!round_capable()) return;
+            launch_rows_hooked(fftk::ROWS_HOOK_PLAIN, hooked_params(0, in, out, nb, inverse, scale, h, kBothEnds, 0), passes[0]);
             rt->mark(0);
             return;
         }
@@ -1514,13 +1539,13 @@ class Pow2Plan {
             const int cb = (nb - b0) < chunk ? (nb - b0) : chunk;
             const cpx<T>* src = in + (size_t)b0 * (size_t)ip;
             cpx<T>* dst = out + (size_t)b0 * (size_t)op;
-            launch_pass_hooked(0, src, scratch, cb, inverse, (T)1, h, 1, 0);
+            launch_pass_hooked(0, src, scratch, cb, inverse, (T)1, h, fftk::HOOKBIT_LOAD, 0);
             rt->mark(0);
             if (passes.size() == 3) {
                 launch_pass(1, scratch, scratch, cb, inverse, (T)1);
                 rt->mark(1);
             }
-            launch_pass_hooked(last, scratch, dst, cb, inverse, scale, h, 2, (long long)b0 * h.post_tab_b);
+            launch_pass_hooked(last, scratch, dst, cb, inverse, scale, h, fftk::HOOKBIT_STORE, (long long)b0 * h.post_tab_b);
             rt->mark((int)last);
         }
     }

@@ -40,7 +40,7 @@ FFT_ROWS_FIXED_LIST(FFT_EXTERN_FIXED)
 FFT_ROWS_FIXED8_LIST(FFT_EXTERN_FIXED8)
 #undef FFT_EXTERN_FIXED8
 #define FFT_EXTERN_FILTER(T) \
-    extern template __global__ void tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, FFT_ROWS_FILTER_HOOK>(TileParams<T>);
+    extern template __global__ void tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, ROWS_HOOK_BITS_FILTER>(TileParams<T>);
 FFT_ROWS_FILTER_LIST(FFT_EXTERN_FILTER)
 #undef FFT_EXTERN_FILTER
 }  // namespace fftk

@@ -71,6 +71,33 @@ enum { FAM_SR16 = 0, FAM_R4 = 1, FAM_R2 = 2 };
 // HOOK_MUL_PAIR (load side of the real-frames kernel only): the table entry is a PAIR of real factors, applied component by component
 // (re *= w.re, im *= w.im) -- not a complex product.
 enum { HOOK_NONE = 0, HOOK_MUL = 1, HOOK_MUL_CONJ = 2, HOOK_ABS2 = 3, HOOK_MUL_PAIR = 4 };
+// The bits of tile_fft_kernel's HOOK template parameter (0: no hooks).  Compile-time bits: an instantiation without one compiles to
+// the code it had before.  "rows kernel" = the hooked single-pass rows kernel, E = 4, radix-4, LOAD_LCONTIG / STORE_LCONTIG, H = 1,
+// no inter-pass twiddle; its variants are listed in fft_rows_list.h (FFT_ROWS_HOOK_LIST).  What a bit reads is said at its fields
+// of TileHooks below.  The names stand in the order of their bit numbers, LOAD = bit 0 ... VALID = bit 9 (older documents and the
+// docstrings of the frames, real frames, inverse frames and filter tests still say "HOOK bit 6" for HOOKBIT_REAL, "bit 7" for _HERM,
+// "bits 8 and 9" for _BOUND and _VALID).
+//   bit             what it compiles in                                          where, and with what
+//   HOOKBIT_LOAD    the load side: pre_tab / pre_mode, n_in, in_vec_ok           any tile kernel
+//   HOOKBIT_STORE   the store side: post_tab / post_mode, n_out, out_vec_ok      any tile kernel
+//   HOOKBIT_TABPF   the load-side table values are prefetched together with      with LOAD; the 2-waves-per-SIMD multi-pass kernels
+//                   the data (+ E * 4 VGPRs per group); without it they are      (the rows kernel's 128-VGPR budget has no room);
+//                   read when the data is consumed                               never with REAL, HERM, BOUND
+//   HOOKBIT_ROUND   FFT -> mid product -> inverse FFT in one kernel (mid_tab)    single-pass kernel; never with REAL, HERM
+//   HOOKBIT_FRAMES  framed load: the columns are overlapping frames of signals   rows kernel, with LOAD and STORE; never with HERM
+//   HOOKBIT_POWER   one-sided power store (power_out) instead of complex bins    rows kernel, with LOAD, STORE, FRAMES; never with
+//                                                                                HERM, BOUND
+//   HOOKBIT_REAL    real frames: packed real load, r2c split in the store        rows kernel, with LOAD, STORE, FRAMES; never with
+//                                                                                TABPF, ROUND, HERM, BOUND
+//   HOOKBIT_HERM    Hermitian rows load: one-sided rows in, the c2r merge on     rows kernel, with LOAD; never with TABPF, ROUND,
+//                   the way to the stages                                        FRAMES, POWER, REAL
+//   HOOKBIT_BOUND   bounded framed load (overlap-save blocks, zero outside the   rows kernel, not FIXED, with LOAD and FRAMES; never
+//                   signal)                                                      with TABPF, POWER, REAL, HERM
+//   HOOKBIT_VALID   valid-part framed store (the wrap of every block dropped)    as BOUND, with BOUND and STORE
+enum {
+    HOOKBIT_LOAD = 1, HOOKBIT_STORE = 2, HOOKBIT_TABPF = 4, HOOKBIT_ROUND = 8, HOOKBIT_FRAMES = 16, HOOKBIT_POWER = 32, HOOKBIT_REAL = 64,
+    HOOKBIT_HERM = 128, HOOKBIT_BOUND = 256, HOOKBIT_VALID = 512
+};
 template <typename T>
 struct TileHooks {
     const cpx<T>* pre_tab;
@@ -80,49 +107,49 @@ struct TileHooks {
     int n_out;             // outputs stored per transform
     int pre_mode, post_mode;
     int in_vec_ok, out_vec_ok;  // 16-byte accesses allowed on the user's side (rows 16-byte aligned: even pitch for fp32)
-    // HOOK bit 3 (single-pass kernel only): FFT -> spectral product -> inverse FFT in ONE kernel.  After the forward stages the
+    // HOOKBIT_ROUND (single-pass kernel only): FFT -> spectral product -> inverse FFT in ONE kernel.  After the forward stages the
     // spectrum is multiplied by mid_tab[K] (one table for the whole batch; mid_mode as post_mode, HOOK_ABS2 needs none), the
     // inverse transform runs on the registers (a thread holds the same index set before and after a transform) and the result
     // goes through the store side above (post_tab / n_out), scaled by TileParams::scale.
     const cpx<T>* mid_tab;
     int mid_mode;
-    // HOOK bit 4 (single-pass kernel only): FRAMED load.  Tile column t is frame f = c0 + t of the execute, and its samples start at
+    // HOOKBIT_FRAMES (single-pass kernel only): FRAMED load.  Tile column t is frame f = c0 + t of the execute, and its samples start at
     // in + (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_c: overlapping frames (in_c = the hop) of
     // many signals.  frames_rcp = ceil(2^32 / frames_per_signal): the quotient is one multiply-high, exact for every f the
     // launcher lets through (f * frames_per_signal < 2^32); unused when frames_per_signal == 1.
     int frames_per_signal;
     unsigned frames_rcp;
     long long signal_pitch;
-    // HOOK bit 5 (single-pass kernel only): ONE-SIDED POWER store.  Instead of complex bins the store side writes reals,
+    // HOOKBIT_POWER (single-pass kernel only): ONE-SIDED POWER store.  Instead of complex bins the store side writes reals,
     // power_out[f * (L/2 + 1) + k] = |X[k]|^2 * power_scale, doubled for 0 < k < L/2, k <= L/2 only (reference
     // applications/power_spectrum.c:75-80).  Rows of L/2 + 1 values start only sizeof(T)-aligned: scalar stores.
     T* power_out;
     T power_scale;
-    // HOOK bit 6 (single-pass kernel only, with bits 0, 1 and 4): REAL FRAMES.  `in` is an array of REAL samples and frame f starts at
+    // HOOKBIT_REAL (single-pass kernel only, with LOAD, STORE and FRAMES): REAL FRAMES.  `in` is an array of REAL samples and frame f starts at
     // real sample (f / frames_per_signal) * signal_pitch + (f % frames_per_signal) * in_c of it (hop and pitch count reals).  A
     // frame of n = 2 L reals is loaded as the L complex values z[m] = y[2m] + i y[2m+1] (the reals read as pairs; pre_mode =
     // HOOK_MUL_PAIR, pre_tab[m] = (w[2m], w[2m+1]), n_in = L) and the store side splits the length-L spectrum Z into the
     // L + 1 non-redundant bins of the length-n real transform (Z[L] = Z[0]):
     //   E = (Z[k] + conj Z[L-k]) / 2,  O = (Z[k] - conj Z[L-k]) / (2i),  X[k] = E + W_n^k O,  W_n^k = post_tab[k], k < L
     //   X[0] = Re Z[0] + Im Z[0],  X[L] = Re Z[0] - Im Z[0]   (imaginary parts exactly 0)
-    // Rows of L + 1 bins: complex at out + f * out_c, or with bit 5 one-sided power rows at power_out + f * (L + 1)
+    // Rows of L + 1 bins: complex at out + f * out_c, or with HOOKBIT_POWER one-sided power rows at power_out + f * (L + 1)
     // (|X[k]|^2 * power_scale, doubled for 0 < k < L).  Rows start only sizeof(cpx<T>)- / sizeof(T)-aligned: per-value stores.
-    // HOOK bit 7 (single-pass kernel only, with bit 0; never with bits 2 to 6): HERMITIAN ROWS load, the mirror image of bit 6's
-    // store.  Tile column t is frame f = c0 + t and reads the one-sided row in + f * in_c of L + 1 bins (in_c = L + 1, n_in = L)
+    // HOOKBIT_HERM (single-pass kernel only, with LOAD; never with TABPF ... REAL): HERMITIAN ROWS load, the mirror image of
+    // HOOKBIT_REAL's store.  Tile column t is frame f = c0 + t and reads the one-sided row in + f * in_c of L + 1 bins (in_c = L + 1, n_in = L)
     // of a length-2L real transform; the column the stages start from is the c2r merge of that row,
     //   E = (X[k] + conj X[L-k]) / 2,  O = (X[k] - conj X[L-k]) / 2 * conj(W_n^k),  Z[k] = E + i O,  W_n^k = pre_tab[k], k < L
     // with X[0] and X[L] taken as REAL (their imaginary parts are never used: Re X[L] travels in the imaginary slot of X[0]).  The
     // mirrored bin X[L-k] is read from the frame's own LDS row once the tile has landed.  pre_mode is HOOK_NONE: pre_tab is the
     // merge's table, not a factor.  With inverse = 1 and scale = 1 / L the column that leaves is the frame's 2L real samples.
     // Rows of L + 1 bins start only sizeof(cpx<T>)-aligned: in_vec_ok is 0 in fp32 (value-by-value loads).
-    // HOOK bit 8 (single-pass kernel only, with bits 0 and 4): BOUNDED framed load, the input side of overlap-save filtering.  Block
-    // (sig, w) of bit 4's split starts frame_lead samples BEFORE sample w * in_c of its signal: sample l of the block is the signal's
+    // HOOKBIT_BOUND (single-pass kernel only, with LOAD and FRAMES): BOUNDED framed load, the input side of overlap-save filtering.  Block
+    // (sig, w) of the framed load's split starts frame_lead samples BEFORE sample w * in_c of its signal: sample l of the block is the signal's
     // sample q = w * in_c - frame_lead + l (long long), read only if 0 <= q < signal_len and zero otherwise -- memory outside the
     // signal is never touched.  16-byte loads only for chunks wholly inside [0, signal_len) at a 16-byte aligned address (in_vec_ok
     // then says: base and pitch are aligned); everything else value by value.  No load-side table (pre_mode = HOOK_NONE).
     int frame_lead;
     int signal_len;
-    // HOOK bit 9 (single-pass kernel only, with bits 1, 4 and 8): VALID-PART framed store.  Value l of block (sig, w) goes to
+    // HOOKBIT_VALID (single-pass kernel only, with STORE, FRAMES and BOUND): VALID-PART framed store.  Value l of block (sig, w) goes to
     // out + sig * out_signal_pitch + p, p = w * in_c + l - frame_lead - out_off, only if l >= frame_lead and 0 <= p < out_len: the
     // first frame_lead values of every block (the circular wrap) are dropped, the rest lands in the output signal where it belongs.
     // 16-byte stores only where the destination chunk is aligned and wholly valid (out_vec_ok: base and pitch aligned).
@@ -169,7 +196,7 @@ struct TileParams {
     // TEAM_STATUS_NO_TEAMS (1) in the word, i.e. gave up before touching anything
     const unsigned* run_if;
     T scale;      // applied at the store (1/N folded into the last pass)
-    TileHooks<T> hk;  // read only by HOOK = true instantiations
+    TileHooks<T> hk;  // read only by HOOK != 0 instantiations
 };
 
 template <int X>
@@ -512,14 +539,7 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 
 // FIXED != 0 bakes (log2L << 8 | log2C) into the instantiation: every LDS offset becomes an immediate and the
 // stage loop unrolls (fewer address VGPRs, less integer VALU); FIXED == 0 reads both from the parameters.
-// HOOK: 0 none; bit 0 the load side of TileHooks is compiled in, bit 1 the store side, bit 2 the load-side table values
-// are prefetched together with the data (+ E * 4 VGPRs per group: the 2-waves-per-SIMD kernels; without it they are read
-// when the data is consumed -- the 4-waves-per-SIMD rows kernel, whose 128-VGPR budget has no room for them), bit 3 FFT ->
-// product -> inverse FFT in one kernel, bit 4 framed load, bit 5 one-sided power store, bit 6 real frames: packed real load and
-// the r2c split in the store, bit 7 Hermitian rows load: one-sided rows in, the c2r merge on the way to the stages (TileHooks;
-// the last five on the hooked single-pass rows kernel only, bit 6 only with bits 0, 1 and 4, bit 7 with bit 0 and none of bits
-// 2 to 6), bit 8 bounded framed load and bit 9 valid-part framed store: overlap-save filtering, with bits 0, 1, 3 and 4 and none of the
-// others.  Compile-time bits: an instantiation without one compiles to the code it had before.
+// HOOK: a set of HOOKBIT_* (the table above TileHooks); 0: none.
 // waves per SIMD the register budget of an instantiation is sized for.  The fp32 kernels with their shape baked in need only
 // 92-122 VGPRs when built for four waves per SIMD (no spills; built for two they take 150-250 because they may), i.e. two
 // 512-thread workgroups per CU.  Measured (profiles/r2_ab_rows_fixed.txt): the single-pass rows kernel gains 5...12 % from
@@ -530,7 +550,7 @@ FFT_DEVICE TileCoord<T> tile_coord(const TileParams<T>& p, long long tile) {
 template <typename T, int E, int LOADM, int STOREM, int FIXED, int HOOK>
 constexpr int tile_waves_per_simd() {
     if (E == 4) return FFT_WAVES_PER_SIMD_E4;
-    if (sizeof(T) != 4 || FIXED == 0 || (HOOK & 4)) return FFT_WAVES_PER_SIMD;
+    if (sizeof(T) != 4 || FIXED == 0 || (HOOK & HOOKBIT_TABPF)) return FFT_WAVES_PER_SIMD;
     if (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG) return (FIXED >> 8) >= 10 ? FFT_WAVES_PER_SIMD_ROWS8 : FFT_WAVES_PER_SIMD;  // rows kernel: n = 512 loses 6 %
     return FFT_WAVES_PER_SIMD_FIX32;
 }
@@ -590,20 +610,20 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
 #endif
     constexpr int DEPTH = FFT_DEPTH;  // 2 = double-buffered prefetch (+32 VGPRs; needs FFT_FORCE_OPAQUE to stay spill-free)
     vec16<T> nxtbuf[DEPTH][H][E];
-    constexpr bool HK_LOAD = (HOOK & 1) != 0, HK_STORE = (HOOK & 2) != 0, HK_TABPF = (HOOK & 4) != 0, HK_ROUND = (HOOK & 8) != 0;
-    constexpr bool HK_FRAMES = (HOOK & 16) != 0, HK_POWER = (HOOK & 32) != 0;  // TileHooks: framed load, one-sided power store
-    constexpr bool HK_REAL = (HOOK & 64) != 0;  // TileHooks: real frames (packed real load, r2c split in the store)
+    constexpr bool HK_LOAD = (HOOK & HOOKBIT_LOAD) != 0, HK_STORE = (HOOK & HOOKBIT_STORE) != 0, HK_TABPF = (HOOK & HOOKBIT_TABPF) != 0, HK_ROUND = (HOOK & HOOKBIT_ROUND) != 0;
+    constexpr bool HK_FRAMES = (HOOK & HOOKBIT_FRAMES) != 0, HK_POWER = (HOOK & HOOKBIT_POWER) != 0;  // TileHooks: framed load, one-sided power store
+    constexpr bool HK_REAL = (HOOK & HOOKBIT_REAL) != 0;  // TileHooks: real frames (packed real load, r2c split in the store)
     static_assert(!(HK_FRAMES || HK_POWER || HK_REAL) || (LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && HK_LOAD && HK_STORE),
                   "frames / power hooks: the hooked single-pass rows kernel only");
     static_assert(!HK_REAL || (HK_FRAMES && !HK_TABPF && !HK_ROUND && H == 1), "real frames: with the framed load on the hooked single-pass rows kernel only");
-    constexpr bool HK_HERM = (HOOK & 128) != 0;  // TileHooks: Hermitian rows load (one-sided rows in, the c2r merge before the stages)
+    constexpr bool HK_HERM = (HOOK & HOOKBIT_HERM) != 0;  // TileHooks: Hermitian rows load (one-sided rows in, the c2r merge before the stages)
     static_assert(!HK_HERM || (E == 4 && FAM == FAM_R4 && LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && H == 1 && !TWIDDLE && HK_LOAD &&
-                               !(HOOK & (4 | 8 | 16 | 32 | 64))),
-                  "Hermitian rows load: on the hooked single-pass rows kernel only, with the load side and none of bits 2 to 6");
-    constexpr bool HK_BOUND = (HOOK & 256) != 0, HK_VALID = (HOOK & 512) != 0;  // TileHooks: bounded framed load, valid-part framed store
+                               !(HOOK & (HOOKBIT_TABPF | HOOKBIT_ROUND | HOOKBIT_FRAMES | HOOKBIT_POWER | HOOKBIT_REAL))),
+                  "Hermitian rows load: on the hooked single-pass rows kernel only, with the load side and none of TABPF, ROUND, FRAMES, POWER, REAL");
+    constexpr bool HK_BOUND = (HOOK & HOOKBIT_BOUND) != 0, HK_VALID = (HOOK & HOOKBIT_VALID) != 0;  // TileHooks: bounded framed load, valid-part framed store
     static_assert(!(HK_BOUND || HK_VALID) || (E == 4 && H == 1 && FAM == FAM_R4 && LOADM == LOAD_LCONTIG && STOREM == STORE_LCONTIG && !TWIDDLE &&
-                                              FIXED == 0 && HK_LOAD && HK_FRAMES && !(HOOK & (4 | 32 | 64 | 128))),
-                  "bounded framed load / valid-part store: on the hooked single-pass rows kernel only, with the framed load and none of bits 2, 5, 6, 7");
+                                              FIXED == 0 && HK_LOAD && HK_FRAMES && !(HOOK & (HOOKBIT_TABPF | HOOKBIT_POWER | HOOKBIT_REAL | HOOKBIT_HERM))),
+                  "bounded framed load / valid-part store: on the hooked single-pass rows kernel only, with the framed load and none of TABPF, POWER, REAL, HERM");
     static_assert(!HK_VALID || (HK_BOUND && HK_STORE), "valid-part framed store: with the store side and the bounded framed load");
     vec16<T> nxttab[HK_TABPF ? DEPTH : 1][HK_TABPF ? H : 1][HK_TABPF ? E : 1];  // the load-side table values of the same chunks
     const bool pre_on = HK_LOAD && p.hk.pre_mode != HOOK_NONE;  // wave-uniform
@@ -810,7 +830,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                         x[h][e][vv] = *reinterpret_cast<const cpx<T>*>(smem + h * group_bytes + (size_t)(V * j + vv) * pitch +
                                                                        (size_t)l * SZ);
                     if (HK_HERM) {
-                        // c2r merge of the frame's one-sided row (TileHooks, bit 7): slot e takes Z[l] from X[l] and X[L - l], both in the
+                        // c2r merge of the frame's one-sided row (TileHooks, HOOKBIT_HERM): slot e takes Z[l] from X[l] and X[L - l], both in the
                         // frame's own LDS row, complete since the barrier above: no new barrier.  Element 0 of the row is (Re X[0], Re X[L]).
                         // Padding columns hold zeros and merge to zeros.
                         FFT_UNROLL
@@ -998,7 +1018,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                         const int t = h * CG + (g >> log2CPR);
                         const int pos = g & cpr_mask;
                         if (HK_VALID) {
-                            // valid part of block (sig, w) = column c0 + t (TileHooks, bit 9): values l = pos * V ... go to sample
+                            // valid part of block (sig, w) = column c0 + t (TileHooks, HOOKBIT_VALID): values l = pos * V ... go to sample
                             // p0 ... of the signal's output.  Columns at or past n_cols store nothing; every store sits under
                             // l >= frame_lead and 0 <= p < out_len, so no byte outside the out_len samples of a signal is written.
                             const int l0 = pos * V, lead = p.hk.frame_lead;
@@ -1020,7 +1040,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS2((E == 4 ? 1024 : 512), (tile_waves_per_simd<T
                                 }
                             }
                         } else if (HK_REAL) {
-                            // r2c split of frame c0 + t (TileHooks, bit 6): bins k = pos * V ... of its L + 1.  Z[k] is this thread's own chunk,
+                            // r2c split of frame c0 + t (TileHooks, HOOKBIT_REAL): bins k = pos * V ... of its L + 1.  Z[k] is this thread's own chunk,
                             // Z[L - k] lies in the SAME LDS row, complete since the barrier above: no new barrier.  The pos == 0 thread also
                             // writes bin L.  Columns at or past n_cols -- the ragged last tile's, and a short batch's padding -- were loaded as
                             // zeros without touching memory and write nothing: every store below sits under this one predicate.

@@ -450,7 +450,7 @@ FFT_KERNEL void FFT_LAUNCH_BOUNDS(512) copy_dma_kernel(const vec16<float>* in, v
 #endif
 
 // ---------------------------------------------------------------------------
-// Overlap-save filtering, the unfused ends (FilterPlan's fallback; the fused kernel is tile_fft_kernel with HOOK bits 8 and 9 and
+// Overlap-save filtering, the unfused ends (FilterPlan's fallback; the fused kernel is tile_fft_kernel with HOOKBIT_BOUND and HOOKBIT_VALID and
 // has the same predicates).  Block f = sig * nb + w of length n = 2^log2n holds the signal's samples q = w * B - lead + l, l < n,
 // zero where q lies outside [0, signal_len); of its circular convolution with the taps the values l >= lead are samples
 // p = w * B + l - lead - out_off of the signal's output, stored only for 0 <= p < out_len.  One thread per value; blocks

@@ -447,12 +447,21 @@ class FusedPlan {
 //   FRAMES_STFT out[s][w][k], k <= n/2 complex; POWER / WELCH as above.  The core is the transform of HALF the length, L = n/2, on
 //   z[m] = y[2m] + i y[2m+1] (y the windowed frame: the reals read as complex pairs, the window table packed the same way), and
 //   the split  E = (Z[k] + conj Z[L-k]) / 2, O = (Z[k] - conj Z[L-k]) / (2i), X[k] = E + W_n^k O  yields the n/2 + 1 bins.
-//   Where L fits one hook-capable pass the split rides in that pass's store (tile_fft_kernel HOOK bit 6: both Z[k] and Z[L-k] of a
+//   Where L fits one hook-capable pass the split rides in that pass's store (tile_fft_kernel's HOOKBIT_REAL: both Z[k] and Z[L-k] of a
 //   frame lie in one LDS row there): one launch reads the reals in place and writes the one-sided rows.  Every other n, and
 //   no_fusion: frames_pack_real_kernel (windowed frames -> [frames][L] complex), the plain core, r2c_split_kernel, and for POWER /
 //   WELCH psd_onesided_rows_kernel -- correct, not tuned.
 // ---------------------------------------------------------------------------
 enum FramesOut { FRAMES_STFT = 0, FRAMES_POWER = 1, FRAMES_WELCH = 2 };
+
+// the load side every frames execute shares: frames of n_in samples of the core, `hop` apart, times the window `win` on the way in (NULL: none)
+template <typename T>
+ExecHooks<T> frame_hooks(const cpx<T>* win, int win_mode, long long n_in, long long hop) {
+    ExecHooks<T> f;
+    f.pre_tab = win; f.pre_mode = win_mode;
+    f.n_in = n_in; f.in_pitch = hop;
+    return f;
+}
 
 template <typename T, typename RT>
 class FramesPlan {
@@ -544,9 +553,7 @@ class FramesPlan {
         if (real_input) {
             const int h = n / 2;
             if (fused()) {
-                ExecHooks<T> f;
-                f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL_PAIR;
-                f.n_in = h; f.in_pitch = hop;
+                ExecHooks<T> f = frame_hooks<T>(win, fftk::HOOK_MUL_PAIR, h, hop);
                 f.frames_per_signal = nw; f.signal_pitch = signal_pitch;
                 f.real_frames = true; f.post_tab = wsplit; f.out_pitch = hb;
                 if (out_kind == FRAMES_STFT) {
@@ -571,9 +578,7 @@ class FramesPlan {
                     launch_flat(rt, fftk::psd_onesided_rows_kernel<T>, nf * hb, (const cpx<T>*)X, (long long)hb, rows, hb, scale, nf * hb);
             }
         } else if (fused()) {
-            ExecHooks<T> f;
-            f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL;
-            f.n_in = n; f.in_pitch = hop;
+            ExecHooks<T> f = frame_hooks<T>(win, fftk::HOOK_MUL, n, hop);
             f.frames_per_signal = nw; f.signal_pitch = signal_pitch;
             if (out_kind == FRAMES_STFT) {
                 core.execute_frames(x, (cpx<T>*)out, (int)nf, f);
@@ -590,9 +595,7 @@ class FramesPlan {
             }
             const bool aligned = (signal_pitch % V) == 0 && ((uintptr_t)x & 15) == 0;  // every signal starts 16-byte aligned
             if (core.hook_capable() && aligned) {
-                ExecHooks<T> f;
-                f.pre_tab = win; f.pre_mode = fftk::HOOK_MUL;
-                f.n_in = n; f.in_pitch = hop;
+                const ExecHooks<T> f = frame_hooks<T>(win, fftk::HOOK_MUL, n, hop);
                 for (int s = 0; s < n_signals; s++)
                     core.execute_hooked(x + (long long)s * signal_pitch, stage + (long long)s * nw * n, nw, false, f);
             } else {
@@ -622,7 +625,7 @@ class FramesPlan {
 //   sample cannot be recovered: inv_env[t] = 0 and y[s][t] is written as exactly 0 (`unrecoverable` counts them per signal).
 //   Signal s starts at y + s * signal_pitch reals.
 // The core is the inverse transform of HALF the length, L = n/2, on the c2r merge of every row (RealPlan's identity).  Where L fits
-// one hook-capable pass the merge rides in that pass's load (tile_fft_kernel HOOK bit 7): one launch turns the rows into the
+// one hook-capable pass the merge rides in that pass's load (tile_fft_kernel's HOOKBIT_HERM): one launch turns the rows into the
 // [frames][n] real workspace.  Every other n (n = 4 included), and no_fusion: iframes_merge_kernel and the plain core in place on
 // the workspace -- correct, not tuned.  frames_overlap_add_kernel then writes the signals.
 // ---------------------------------------------------------------------------
@@ -711,7 +714,6 @@ class IFramesPlan {
         const int h = n / 2;
         if (fused()) {
             ExecHooks<T> f;
-            f.herm_rows = true;
             f.pre_tab = wmerge;
             core.execute_iframes(X, work, (int)nf, f);
         } else {
@@ -737,7 +739,7 @@ class IFramesPlan {
 //   y[p] = full[p + out_off], p < out_len;  nb = ceil((out_off + out_len) / B) blocks per signal.
 // FFT_n(h) is computed once at plan time by the plan's own core.  Where n fits one hook-capable pass: ONE launch of the hooked
 // single-pass kernel over all n_signals * nb blocks (bounded framed load, spectral product and inverse on the registers, valid-part
-// framed store: tile_fft_kernel HOOK bits 8 and 9) -- one HBM round trip of the user's data, no [blocks][n] copy in or out.  Every
+// framed store: tile_fft_kernel's HOOKBIT_BOUND and HOOKBIT_VALID) -- one HBM round trip of the user's data, no [blocks][n] copy in or out.  Every
 // other n, a block count frames_exact() refuses, no_fusion and no_chain: filter_gather_kernel -> the core's forward . H . inverse
 // (one kernel, chained or hooked, as FusedPlan's circular convolution runs them) -> filter_scatter_kernel on chunks of blocks, so
 // the workspace stays bounded -- correct, not tuned.
@@ -852,7 +854,6 @@ class FilterPlan {
         if (x0 < y1 && y0 < x1) return -1;
         if (fused()) {
             ExecHooks<T> f;
-            f.filter = true;
             f.in_pitch = B;
             f.frames_per_signal = nb; f.signal_pitch = x_pitch;
             f.frame_lead = lead; f.signal_len = signal_len;
@@ -1244,14 +1245,14 @@ class CrossFramesPlan {
 // of a matrix are dense.  Input and output must not overlap; the input is never written.
 //
 // Fused path: two launches on half-size data.  L = cols/2, hb = L + 1, P = rows.
-//   forward  1  rows     ONE launch of the hooked single-pass rows kernel over rows * M frames of cols reals (tile_fft_kernel HOOK bit 6:
+//   forward  1  rows     ONE launch of the hooked single-pass rows kernel over rows * M frames of cols reals (tile_fft_kernel's HOOKBIT_REAL:
 //                        packed real load where the image lies -- any base, any matrix pitch -- r2c split in the store) -> the one-sided
 //                        rows of the work image [M][rows][ld], ld = L + V: its rows are 16-byte aligned
 //            2  columns  tile_fft_colpass_kernel over hb live columns: 16-byte loads from the work image, stores straight into the
 //                        caller's [M][rows][hb] (value by value in fp32, where those rows are only 8-byte aligned)
 //   inverse  1  columns  tile_fft_colpass_kernel, inverse, scale 1 / P: the caller's X (value by value in fp32) -> work image
-//                        [M][rows][hb] -- the pitch the Hermitian rows load reads (ExecHooks::herm_rows fixes it at L + 1)
-//            2  rows     ONE launch of the hooked rows kernel with HOOK bit 7, inverse, scale 1 / L -> the real rows, straight into the
+//                        [M][rows][hb] -- the pitch the Hermitian rows load reads (execute_iframes fixes it at L + 1)
+//            2  rows     ONE launch of the hooked rows kernel with HOOKBIT_HERM, inverse, scale 1 / L -> the real rows, straight into the
 //                        caller's x where that is dense and 16-byte aligned; otherwise into an image of the plan's own and from there
 //                        by real2d_copy_kernel (a third launch: the rows kernel stores 16 bytes at a time)
 // taken where cols is a power of two whose half fits ONE hook-capable pass (FramesPlan's criterion: core.round_capable() and
@@ -1319,7 +1320,7 @@ class Real2DPlan {
   public:
     static constexpr int SZ = (int)sizeof(cpx<T>);
     static constexpr int V = 16 / SZ;
-    // the longest half-row the fused path takes: what the hooked rows kernel's bits 6 and 7 are checked at (the real frames plans' tests
+    // the longest half-row the fused path takes: what the hooked rows kernel's HOOKBIT_REAL and HOOKBIT_HERM are checked at (the real frames plans' tests
     // stop at frames of 8192 reals in fp32, 4096 in fp64).  A device whose LDS holds one pass of 4096 fp64 points still takes the
     // fallback there, as FilterPlan does beyond its kNmax
     static constexpr int kLmax = SZ == 8 ? 4096 : 2048;
@@ -1437,8 +1438,7 @@ class Real2DPlan {
         cpx<T>* X_out = (cpx<T>*)out;
         if (fused()) {
             if (forward) {
-                ExecHooks<T> f;
-                f.n_in = L; f.in_pitch = cols;
+                ExecHooks<T> f = frame_hooks<T>(nullptr, fftk::HOOK_NONE, L, cols);
                 f.frames_per_signal = rows; f.signal_pitch = in_pitch;
                 f.real_frames = true; f.post_tab = wtab; f.out_pitch = ld;
                 core.execute_frames(reinterpret_cast<const cpx<T>*>(x_in), work, (int)frames(), f);
@@ -1451,7 +1451,6 @@ class Real2DPlan {
                 const bool ivec = (i0 & 15) == 0 && (hb % V) == 0 && (in_pitch % V) == 0;
                 cstep.run(X_in, hb, in_pitch, ivec, work, ld, (long long)rows * ld, (ld % V) == 0, M, true, (T)(1.0L / (long double)rows));
                 ExecHooks<T> g;
-                g.herm_rows = true;
                 g.pre_tab = wtab;
                 core.execute_iframes(work, reinterpret_cast<cpx<T>*>(direct ? x_out : rout), (int)frames(), g);
                 if (!direct) copy<T>(rout, rm, x_out, out_pitch, rm);

@@ -17,7 +17,7 @@ FFT_ROWS_FIXED_LIST(FFT_INSTANTIATE_FIXED)
 FFT_ROWS_FIXED8_LIST(FFT_INSTANTIATE_FIXED8)
 #undef FFT_INSTANTIATE_FIXED8
 #define FFT_INSTANTIATE_FILTER(T) \
-    template __global__ void tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, FFT_ROWS_FILTER_HOOK>(TileParams<T>);
+    template __global__ void tile_fft_kernel<T, 4, 1, FAM_R4, LOAD_LCONTIG, STORE_LCONTIG, false, 0, ROWS_HOOK_BITS_FILTER>(TileParams<T>);
 FFT_ROWS_FILTER_LIST(FFT_INSTANTIATE_FILTER)
 #undef FFT_INSTANTIATE_FILTER
 }  // namespace fftk
