@@ -320,9 +320,10 @@ struct PlanSet {
     ffteng::Real2DPlan<T, HipRT>* real2d = nullptr;         // rfft2 / irfft2 of real images
     ffteng::DctPlan<T, HipRT>* dct = nullptr;               // DCT / DST of types II and III on batched real rows
     ffteng::Dct2DPlan<T, HipRT>* dct2d = nullptr;           // ... along both axes of real images
+    ffteng::Plan3D<T, HipRT>* three_d = nullptr;            // 3D complex transforms of volumes
     template <class F>
     void each(F&& f) {
-        f(pow2); f(blue); f(mixed); f(two_d); f(real); f(fused); f(frames); f(iframes); f(cross); f(filter); f(conv2d); f(real2d); f(dct); f(dct2d);
+        f(pow2); f(blue); f(mixed); f(two_d); f(real); f(fused); f(frames); f(iframes); f(cross); f(filter); f(conv2d); f(real2d); f(dct); f(dct2d); f(three_d);
     }
     // a caller's untyped array as complex / real values of this precision
     static const fftk::cpx<T>* c(const void* v) { return (const fftk::cpx<T>*)v; }
@@ -337,14 +338,14 @@ struct fft_gpu_plan {
     HipRT rt;
     hipStream_t own_stream = nullptr;
     // the PLAN_* below: which execute entry point the plan answers to.  PLAN_C2C: the power-of-two, Bluestein or mixed-radix plan of a
-    // complex 1D transform; PLAN_2D: n = rows * cols, batch = matrices; PLAN_R2C / PLAN_C2R: both a RealPlan
+    // complex 1D transform; PLAN_2D: n = rows * cols, batch = matrices; PLAN_3D: n = depth * rows * cols, batch = volumes; PLAN_R2C / PLAN_C2R: both a RealPlan
     int kind = 0;
     int rows = 0, cols = 0;
     PlanSet<float> set32;
     PlanSet<double> set64;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
-enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11, PLAN_DCT = 12, PLAN_DCT_2D = 13 };
+enum { PLAN_C2C = 0, PLAN_2D = 1, PLAN_R2C = 2, PLAN_C2R = 3, PLAN_FUSED = 4, PLAN_FRAMES = 5, PLAN_IFRAMES = 6, PLAN_CROSS = 7, PLAN_FILTER = 8, PLAN_CONV2D = 9, PLAN_R2C_2D = 10, PLAN_C2R_2D = 11, PLAN_DCT = 12, PLAN_DCT_2D = 13, PLAN_3D = 14 };
 
 namespace {
 
@@ -486,11 +487,12 @@ int run_on_device(fft_gpu_plan* p, F&& call) {
 int plan_enqueue(fft_gpu_plan* p, const void* d_in, void* d_out, int nb = 0) {
     if (!p || !d_in || !d_out || nb > p->batch) return -1;
     const bool part = nb > 0 && nb < p->batch;
-    if (part ? p->kind != PLAN_C2C : p->kind >= PLAN_FUSED) return -1;
+    if (part ? p->kind != PLAN_C2C : (p->kind >= PLAN_FUSED && p->kind != PLAN_3D)) return -1;
     if (!part) nb = p->batch;
     const bool inv = p->dir > 0;
     return run_on_device(p, [&](auto& s) {
         if (p->kind == PLAN_2D) s.two_d->execute(s.c(d_in), s.c(d_out), nb);
+        else if (p->kind == PLAN_3D) return s.three_d->execute(s.c(d_in), s.c(d_out));
         else if (p->kind == PLAN_R2C) s.real->execute_r2c(s.r(d_in), s.c(d_out), nb);
         else if (p->kind == PLAN_C2R) s.real->execute_c2r(s.c(d_in), s.r(d_out), nb);
         else if (s.pow2) s.pow2->execute(s.c(d_in), s.c(d_out), nb, inv);
@@ -784,6 +786,19 @@ fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_di
     return fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, dir, prec, FFT_GPU_ALGO_AUTO);
 }
 fft_gpu_plan_t fft_gpu_plan_2d_hip(int rows, int cols, fft_direction dir) { return fft_gpu_plan_2d_ex_hip(rows, cols, 1, dir, FFT_PREC_F64); }
+
+// 3D complex transform of `n_volumes` row-major [depth][rows][cols] volumes (fft_plans_ext.h Plan3D): AUTO only, 7-smooth lengths follow
+// the smooth policy as fft_gpu_plan_2d_ex_hip's do
+fft_gpu_plan_t fft_gpu_plan_3d_hip(int depth, int rows, int cols, int n_volumes, fft_direction dir, fft_precision_t prec) {
+    if (depth <= 0 || rows <= 0 || cols <= 0 || n_volumes <= 0 || (long long)depth * rows * cols > (1ll << 30)) {
+        fprintf(stderr, "fft_hip: invalid 3D plan arguments (depth=%d rows=%d cols=%d volumes=%d)\n", depth, rows, cols, n_volumes);
+        return NULL;
+    }
+    fft_gpu_plan* p = new_plan_shell(depth * rows * cols, n_volumes, (int)dir, prec, PLAN_3D);
+    if (!p) return NULL;
+    p->rows = rows; p->cols = cols;
+    return make_plan(p, "3D", [&](auto& s) { return construct(p, s.three_d, depth, rows, cols, p->dir, n_volumes, smooth_of(FFT_GPU_ALGO_AUTO) == 1); });
+}
 
 // real-input forward / real-output inverse 1D transforms, n/2 + 1 bins (reference stubs algorithms/auto/fft_auto.c:391-409)
 static fft_gpu_plan_t plan_real(int n, int batch, fft_precision_t prec, bool r2c, fft_gpu_algo_t algo) {
@@ -1460,6 +1475,19 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         info->workspace_bytes += (size_t)2 * (size_t)q->n_matrices * (size_t)q->rows * (size_t)q->cols * sizeof(*q->t1);
         if (q->colp.work) info->workspace_bytes += (size_t)q->colp.batch * (size_t)q->colp.n * sizeof(*q->colp.work);
     };
+    // 3D: n = cols, batch = volumes, factors = {cols, rows, depth}; n_passes = launches per execute; fused: 1 the plane kernel runs;
+    // algo / chunk_batch: the depth route's core (the composition's row core where there is no depth route)
+    auto fill_3d = [&](auto* q) {
+        if (q->dcol) fill(q->dcol);
+        else if (q->dany) fill_any(q->dany);
+        else if (q->comp) fill_any(&q->comp->rowp);
+        info->workspace_bytes = q->workspace_bytes();
+        info->n = q->cols;
+        info->batch = q->n_volumes;
+        info->n_passes = q->launches();
+        info->factors[0] = q->cols; info->factors[1] = q->rows; info->factors[2] = q->depth; info->factors[3] = 0;
+        info->fused = q->fused() ? 1 : 0;
+    };
     auto fill_real = [&](auto* r) { fill_any(&r->core); };  // r2c / c2r: the half-length (even n) or full-length complex core
     // 2D: algo, chunk_batch, bluestein_m describe the row transforms; n_passes / factors the strided column passes
     // (1 direct, 2 two strided passes, 0: columns on the transposed image, or a single row)
@@ -1487,6 +1515,7 @@ int fft_gpu_plan_info_hip(fft_gpu_plan_t p, fft_gpu_plan_info_t* info) {
         if (s.real2d) fill_real2d(s.real2d);
         if (s.dct) fill_dct(s.dct);
         if (s.dct2d) fill_dct2d(s.dct2d);
+        if (s.three_d) fill_3d(s.three_d);
     });
     return 0;
 }

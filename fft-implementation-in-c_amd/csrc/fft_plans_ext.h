@@ -2,7 +2,7 @@
 // (SURVEY.md 8f): 2D complex transforms, real-input / real-output 1D transforms, and the fused consumers of the
 // reference's applications/ (FFT convolution, auto- / cross-correlation, periodogram; STFT, spectrogram and Welch PSD on
 // overlapping frames, the inverse STFT by overlap-add, overlap-save FIR filtering, 2D convolution / spectrum filtering, the real 2D
-// transforms rfft2 / irfft2, and the cosine / sine transforms of types II and III).  Templated on the same runtime policy RT as the engine, so the
+// transforms rfft2 / irfft2, the cosine / sine transforms of types II and III, and 3D complex transforms).  Templated on the same runtime policy RT as the engine, so the
 // unmodified source also runs in the CPU emulation (tests/emu).
 #pragma once
 
@@ -11,6 +11,7 @@
 #include "fft_kernels_conv2d.h"
 #include "fft_kernels_real2d.h"
 #include "fft_kernels_dct.h"
+#include "fft_kernels_plane.h"
 
 namespace ffteng {
 
@@ -1717,6 +1718,215 @@ class Dct2DPlan {
         transpose(t1, rm, t2, rm, rows, cols);
         if (colp.execute(t2, rows, t2, rows) != 0) return -1;
         transpose(t2, rm, out, out_pitch, cols, rows);
+        return 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// 3D complex transform of n_volumes row-major [depth][rows][cols] volumes (cols fastest, contiguous), numpy's fftn / ifftn over the last
+// three axes; in == out allowed.  Two steps: the 2D transform of the depth * n_volumes planes, then the transforms along depth in place
+// on `out`.
+//   planes, fused   rows and cols powers of two >= 8 whose tile fits the LDS budget with at most two strips per step, the layouts with the
+//                   register prefetch (choose_plane; on the MI355X planes up to 8192 values in fp32, 4096 in fp64): ONE launch of
+//                   plane_fft_kernel (fft_kernels_plane.h), in -> out, whole contiguous planes through LDS;
+//   planes, composition (every other shape, and no_fusion)   Plan2D(rows, cols, depth * n_volumes), used unchanged -- correct for every
+//                   shape >= 1 x 1 x 1, not tuned;
+//   depth           the image [depth][rows * cols] of a volume: depth a power of two >= 2 and rows * cols a multiple of V: a column Pow2Plan
+//                   with cols' = rows * cols (one pass, or build_columns2 under Plan2D::build's segment rule); any other depth > 1:
+//                   transpose_kernel, a batched AnyPlan of length depth, transpose_kernel, in a workspace of the plan's own; depth = 1: nothing.
+// smooth: what Plan2D takes (7-smooth lengths that are no power of two on the mixed-radix engine).
+// The inverse is scaled ONCE by 1 / (depth * rows * cols): the plane step carries 1 / (rows * cols) -- in the store of plane_fft_kernel, or in
+// Plan2D's two 1D inverses -- and the depth step 1 / depth, like every 1D inverse of the engine.
+// Limits: depth * rows * cols <= 2^30, and the products the inner plans index with ints stay below 2^31 (Plan2D::build's, and the depth
+// route's batch rows * cols * n_volumes).
+// ---------------------------------------------------------------------------
+template <typename T, typename RT>
+class Plan3D {
+  public:
+    static constexpr int SZ = (int)sizeof(cpx<T>);
+    static constexpr int V = 16 / SZ;
+    static constexpr int kMinSeg = 64;  // Plan2D::build's default: below it the one-pass column tile gives way to build_columns2
+    RT* rt = nullptr;
+    int depth = 0, rows = 0, cols = 0, n_volumes = 0, dir = -1;
+    bool smooth = false;
+    // the plane kernel's tile (choose_plane) and its tables
+    fftk::PlaneParams<T> pk;
+    int pk_threads = 0, pk_smem = 0, pk_npf = 0;
+    bool plane_ok = false;
+    cpx<T>* ptab = nullptr;
+    Plan2D<T, RT>* comp = nullptr;     // the composition's planes (made at the build where the plane kernel does not run, else at the first execute under no_fusion)
+    Pow2Plan<T, RT>* dcol = nullptr;   // depth: strided column passes in place
+    AnyPlan<T, RT>* dany = nullptr;    // or: batched 1D on the transposed volumes
+    cpx<T>* tbuf = nullptr;            // [n_volumes][rows * cols][depth]
+    bool ok = false;
+    bool no_fusion = false;
+    // take tiles without the register prefetch too (more than two strips per step).  Off: measured on the MI355X that layout loses to the
+    // composition (128^3 fp32: 2.02 ms against 1.17 ms, profiles/fft3d_vs_composition.txt), the prefetched layouts win; the emulation's tests turn it on
+    bool take_unprefetched = false;
+    ~Plan3D() {
+        delete comp;
+        delete dcol;
+        delete dany;
+        if (!rt) return;
+        rt->dfree(ptab); rt->dfree(tbuf);
+    }
+    template <class F> void each_core(F&& f) {
+        if (comp) comp->each_core(f);
+        if (dcol) f(dcol);
+        if (dany) dany->each_core(f);
+    }
+    void set_no_fusion(bool v) { no_fusion = v; }
+    bool fused() const { return ok && plane_ok && !no_fusion; }
+    long long planes() const { return (long long)depth * n_volumes; }
+    long long plane_elems() const { return (long long)rows * cols; }
+    int tile_planes() const { return plane_ok ? 1 << pk.log2G : 0; }
+    // launches per execute; exact for power-of-two and mixed-radix lengths, an estimate for a chirp-z transform inside a route (one kernel
+    // where its padded length fits one tile, else its core's passes twice)
+    static int any_launches(const AnyPlan<T, RT>* a) {
+        if (!a) return 0;
+        if (a->p2) return a->p2->passes.empty() ? 1 : (int)a->p2->passes.size();
+        if (a->mr) return (int)a->mr->passes.size();
+        if (!a->bl) return 0;
+        const int c = a->bl->core.passes.empty() ? 1 : (int)a->bl->core.passes.size();
+        return (a->bl->core.hook_capable() && a->bl->core.round_capable()) ? 1 : 2 * c;
+    }
+    int launches() const {
+        int n = 0;
+        if (fused()) n = 1;
+        else if (comp) n = any_launches(&comp->rowp) + (comp->colp ? (int)comp->colp->passes.size() : comp->colt ? 2 + any_launches(comp->colt) : 0);
+        else n = 2;  // (the composition is not made yet: its usual two)
+        if (dcol) n += (int)dcol->passes.size();
+        if (dany) n += 2 + any_launches(dany);
+        return n;
+    }
+    size_t workspace_bytes() const {
+        size_t b = 0;
+        if (tbuf) b += (size_t)n_volumes * (size_t)depth * (size_t)plane_elems() * SZ;
+        if (dcol) b += dcol->scratch_bytes;
+        if (comp && comp->tbuf) b += (size_t)planes() * (size_t)plane_elems() * SZ;
+        return b;
+    }
+
+    // The plane kernel's tile for this shape inside `budget` bytes of LDS (the rule of fft_kernels_plane.h); false: no plane kernel
+    bool choose_plane(int budget) {
+        if (rows < 8 || cols < 8 || (rows & (rows - 1)) != 0 || (cols & (cols - 1)) != 0 || cols * SZ < 64) return false;
+        const int per_thread = 4 * V;  // values of a strip per thread
+        const long long pe = plane_elems();
+        int log2G = 0;  // small planes: several per tile, up to 256 threads' worth -- fewer where the budget asks for it
+        while ((pe << (log2G + 1)) <= 256ll * per_thread && (2ll << log2G) <= planes()) log2G++;
+        const int min_nt = (rows > cols ? rows : cols) / 4;
+        const long long tables = (long long)(rows + cols) * SZ;
+        long long tv = 0, image = 0, nt = 0;
+        for (;; log2G--) {
+            tv = pe << log2G;
+            image = ((long long)rows << log2G) * ((long long)cols * SZ + 16);
+            nt = tv / per_thread;
+            if (nt > 512) nt = 512;
+            while (nt >= min_nt && image + nt * per_thread * SZ + tables > budget) nt >>= 1;
+            if (nt >= min_nt && nt >= 1) break;
+            if (log2G == 0) return false;
+        }
+        memset(&pk, 0, sizeof(pk));
+        pk.log2P = ilog2(rows); pk.log2Q = ilog2(cols); pk.log2G = log2G;
+        pk.log2SR = ilog2(nt * per_thread / cols); pk.log2SC = ilog2(nt * per_thread / rows);
+        pk.off_exch = (int)image; pk.off_tables = (int)(image + nt * per_thread * SZ); pk.tables_bytes = (int)tables;
+        pk.n_planes = planes(); pk.n_tiles = (planes() + (1ll << log2G) - 1) >> log2G;
+        pk.inverse = dir > 0 ? 1 : 0;
+        pk.scale = dir > 0 ? (T)(1.0L / (long double)pe) : (T)1;
+        pk_threads = (int)nt;
+        pk_smem = (int)(image + nt * per_thread * SZ + tables);
+        const long long chunks_per_thread = tv / V / nt;
+        pk_npf = chunks_per_thread <= 8 ? (int)chunks_per_thread : 0;
+        return true;
+    }
+
+    bool build(RT* runtime, int depth_, int rows_, int cols_, int dir_, int n_volumes_, bool smooth_ = false) {
+        rt = runtime; depth = depth_; rows = rows_; cols = cols_; dir = dir_ < 0 ? -1 : 1; n_volumes = n_volumes_; smooth = smooth_;
+        if (depth < 1 || rows < 1 || cols < 1 || n_volumes < 1) return false;
+        const long long pe = plane_elems();
+        if (pe * depth > (1ll << 30) || planes() > 0x7fffffff || planes() * rows > 0x7fffffff || planes() * cols > 0x7fffffff ||
+            pe * n_volumes > 0x7fffffff) return false;
+        if (choose_plane(rt->max_lds_bytes()) && (pk_npf > 0 || take_unprefetched)) {
+            std::vector<cpx<T>> t, u;
+            make_twiddle_table<T>(t, cols, cols, 1);
+            make_twiddle_table<T>(u, rows, rows, 1);
+            t.insert(t.end(), u.begin(), u.end());
+            ptab = (cpx<T>*)rt->dmalloc(t.size() * SZ);
+            if (!ptab) return false;
+            rt->h2d(ptab, t.data(), t.size() * SZ);
+            pk.tables = ptab;
+            plane_ok = true;
+        } else if (!ensure_composition()) {
+            return false;
+        }
+        if (depth > 1) {
+            if ((depth & (depth - 1)) == 0 && pe % V == 0) {
+                dcol = new Pow2Plan<T, RT>();
+                if (!dcol->build_columns(rt, ilog2(depth), (int)pe, n_volumes)) { delete dcol; dcol = nullptr; }
+                if (!dcol || dcol->passes[0].seg_bytes < kMinSeg) {  // (Plan2D::build's rule for many rows)
+                    Pow2Plan<T, RT>* two = new Pow2Plan<T, RT>();
+                    if (two->build_columns2(rt, ilog2(depth), (int)pe, n_volumes)) {
+                        delete dcol;
+                        dcol = two;
+                    } else {
+                        delete two;
+                    }
+                }
+            }
+            if (!dcol) {
+                dany = new AnyPlan<T, RT>();
+                if (!dany->build(rt, depth, dir, (int)(pe * n_volumes), ALGO_AUTO, smooth)) return false;
+                tbuf = (cpx<T>*)rt->dmalloc((size_t)n_volumes * (size_t)depth * (size_t)pe * SZ);
+                if (!tbuf) return false;
+            }
+        }
+        ok = true;
+        return true;
+    }
+
+    bool ensure_composition() {
+        if (comp) return true;
+        comp = new Plan2D<T, RT>();
+        if (!comp->build(rt, rows, cols, dir, (int)planes(), smooth)) { delete comp; comp = nullptr; return false; }
+        return true;
+    }
+
+    void launch_planes(const cpx<T>* in, cpx<T>* out) {
+        fftk::PlaneParams<T> q = pk;
+        q.in = in; q.out = out;
+        auto go = [&](auto kernel) {
+            int per_cu = rt->max_blocks_per_cu(kernel, pk_threads, (size_t)pk_smem);
+            if (per_cu < 1) per_cu = 1;
+            long long grid = (long long)rt->num_cus() * per_cu;
+            if (grid > q.n_tiles) grid = q.n_tiles;
+            rt->launch(kernel, grid, pk_threads, (size_t)pk_smem, q);
+        };
+        if (pk_npf == 4) go(fftk::plane_fft_kernel<T, 4>);
+        else if (pk_npf == 8) go(fftk::plane_fft_kernel<T, 8>);
+        else go(fftk::plane_fft_kernel<T, 0>);
+    }
+    void transpose(const cpx<T>* in, cpx<T>* out, int r, int c) {
+        const long long tiles = (long long)n_volumes * ((r + 31) / 32) * ((c + 31) / 32);
+        const long long grid = tiles > 65536 ? 65536 : tiles;
+        rt->launch(fftk::transpose_kernel<T>, grid, 256, (size_t)(32 * 33 * SZ), in, out, r, c, tiles);
+    }
+
+    // 0 / -1 (the composition could not be made: nothing is launched)
+    int execute(const cpx<T>* in, cpx<T>* out) {
+        if (!ok || !in || !out) return -1;
+        if (fused()) {
+            launch_planes(in, out);
+        } else {
+            if (!ensure_composition()) return -1;
+            comp->execute(in, out, (int)planes());
+        }
+        if (dcol) {
+            dcol->execute(out, out, n_volumes, dir > 0);
+        } else if (dany) {
+            transpose(out, tbuf, depth, (int)plane_elems());
+            dany->execute(tbuf, tbuf, (int)(plane_elems() * n_volumes));
+            transpose(tbuf, out, (int)plane_elems(), depth);
+        }
         return 0;
     }
 };

@@ -50,7 +50,8 @@ SIGNATURES = {
     "fft_gpu_plan_1d": (_vp, [_i, _i, _i]), "fft_gpu_execute": (None, [_vp, _vp, _vp]),
     "fft_gpu_destroy_plan": (None, [_vp]), "fft_gpu_dft_1d": (_i, [_vp, _vp, _i, _i]),
     "fft_gpu_dft_1d_batch": (_i, [_vp, _vp, _i, _i, _i]), "fft_gpu_plan_2d": (_vp, [_i, _i, _i]),
-    "fft_gpu_dft_2d": (_i, [_vp, _vp, _i, _i, _i]), "fft_gpu_get_device_name": (C.c_char_p, []),
+    "fft_gpu_dft_2d": (_i, [_vp, _vp, _i, _i, _i]), "fft_gpu_dft_3d": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    "fft_gpu_plan_3d": (_vp, [_i, _i, _i, _i, _i, _i]), "fft_gpu_get_device_name": (C.c_char_p, []),
     "fft_gpu_get_memory_info": (None, [C.POINTER(_sz), C.POINTER(_sz)]), "fft_gpu_set_device": (_i, [_i]),
     # include/fft_hip.h part 1 (backend set)
     "fft_gpu_init_hip": (_i, []), "fft_gpu_cleanup_hip": (None, []), "fft_gpu_available_hip": (_i, []),
@@ -69,7 +70,7 @@ SIGNATURES = {
     "fft_gpu_execute_ptr_hip": (_i, [_vp, _vp, _vp]), "fft_gpu_plan_sync_hip": (_i, [_vp]),
     "fft_gpu_plan_set_option_hip": (_i, [_vp, _i, _i]), "fft_gpu_set_policy_hip": (_i, [_i, _i, _i]),
     "fft_gpu_mixed_radix_passes_hip": (_i, [_i]), "fft_gpu_set_smooth_policy_hip": (_i, [_i]),
-    "fft_gpu_plan_2d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_2d_ex_hip": (_vp, [_i, _i, _i, _i, _i]),
+    "fft_gpu_plan_3d_hip": (_vp, [_i, _i, _i, _i, _i, _i]), "fft_gpu_plan_2d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_2d_ex_hip": (_vp, [_i, _i, _i, _i, _i]),
     "fft_gpu_plan_r2c_1d_hip": (_vp, [_i, _i, _i]), "fft_gpu_plan_c2r_1d_hip": (_vp, [_i, _i, _i]),
     "fft_gpu_plan_2d_algo_hip": (_vp, [_i, _i, _i, _i, _i, _i]),
     "fft_gpu_plan_r2c_1d_algo_hip": (_vp, [_i, _i, _i, _i]), "fft_gpu_plan_c2r_1d_algo_hip": (_vp, [_i, _i, _i, _i]),
@@ -342,6 +343,14 @@ class ExtPlan:
         return cls(init().fft_gpu_plan_2d_algo_hip(rows, cols, n_matrices, direction, _prec_of(np.dtype(dtype)), algo))
 
     @classmethod
+    def plan3d(cls, depth, rows, cols, n_volumes=1, direction=FFT_FORWARD, dtype=np.complex128):
+        """3D complex plan (fft_gpu_plan_3d_hip): n_volumes row-major [depth][rows][cols] volumes of dtype complex64 / complex128; execute
+        and execute_ptr as a 2D plan's, in place allowed.  info(): fused = 1 where the plane kernel runs, n_passes = launches."""
+        p = cls(init().fft_gpu_plan_3d_hip(depth, rows, cols, n_volumes, direction, _prec_of(np.dtype(dtype))))
+        p.depth, p.rows, p.cols, p.n_volumes, p.dtype = depth, rows, cols, n_volumes, np.dtype(dtype)
+        return p
+
+    @classmethod
     def r2c(cls, n, batch=1, dtype=np.float64, algo=ALGO_AUTO):
         return cls(init().fft_gpu_plan_r2c_1d_algo_hip(n, batch, PREC_F32 if np.dtype(dtype) == np.float32 else PREC_F64, algo))
 
@@ -608,6 +617,31 @@ def fft2d(x, direction=FFT_FORWARD, algo=ALGO_AUTO):
     y = _roundtrip(plan, x3, x3.shape, x3.dtype)
     plan.destroy()
     return y.reshape(x.shape)
+
+
+def _fftn(x, direction, name):
+    x = np.asarray(x)
+    if x.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)) or x.ndim not in (3, 4) or x.size == 0:
+        raise ValueError("%s takes a non-empty complex64 or complex128 array of 3 dimensions, or 4 with the batch first" % name)
+    a = np.ascontiguousarray(x)
+    x4 = a.reshape((-1,) + a.shape[-3:])
+    plan = ExtPlan.plan3d(x4.shape[1], x4.shape[2], x4.shape[3], x4.shape[0], direction, x4.dtype)
+    try:
+        y = _roundtrip(plan, x4, x4.shape, x4.dtype)
+    finally:
+        plan.destroy()
+    return y.reshape(x.shape)
+
+
+def fftn(x):
+    """numpy.fft.fftn over the last three axes of a 3-D complex array, or of a 4-D one whose leading axis is the batch, on the device
+    (ExtPlan.plan3d); the complex dtype is kept."""
+    return _fftn(x, FFT_FORWARD, "fftn")
+
+
+def ifftn(x):
+    """numpy.fft.ifftn over the last three axes: ifftn(fftn(x)) = x."""
+    return _fftn(x, FFT_INVERSE, "ifftn")
 
 
 def rfft(x, algo=ALGO_AUTO):

@@ -59,6 +59,8 @@ int fft_gpu_dft_1d_batch(complex_t* in, complex_t* out, int n, int batch, fft_di
  * one batched 1D execute, columns as the engine's strided column pass, the inverse scaled once by 1 / (rows * cols) -- DESIGN.md 4.5) */
 fft_gpu_plan_t fft_gpu_plan_2d(int rows, int cols, fft_direction direction);
 int fft_gpu_dft_2d(complex_t* in, complex_t* out, int rows, int cols, fft_direction direction);
+/* 3D: one row-major depth x rows x cols volume of host values, numpy's fftn / ifftn (fft_gpu_plan_3d_hip); 0 / -1, -1 without a device */
+int fft_gpu_dft_3d(complex_t* in, complex_t* out, int depth, int rows, int cols, fft_direction direction);
 
 /* information (reference fft_gpu.h:163-177) */
 const char* fft_gpu_get_device_name(void); /* "No GPU" when none */
@@ -97,6 +99,8 @@ int fft_gpu_execute_real2d(fft_gpu_plan_t plan, const void* d_in, long long in_p
 fft_gpu_plan_t fft_gpu_plan_dct(int n, int batch, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
 fft_gpu_plan_t fft_gpu_plan_dct_2d(int rows, int cols, int n_matrices, fft_gpu_dct_t type, fft_gpu_dct_norm_t norm, fft_precision_t prec);
 int fft_gpu_execute_dct(fft_gpu_plan_t plan, const void* d_in, long long in_pitch, void* d_out, long long out_pitch);
+/* 3D complex plans (fft_gpu_plan_3d_hip, fft_hip.h) through the dispatcher */
+fft_gpu_plan_t fft_gpu_plan_3d(int depth, int rows, int cols, int n_volumes, fft_direction direction, fft_precision_t prec);
 #ifdef __cplusplus
 }
 #endif

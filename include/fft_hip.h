@@ -178,6 +178,17 @@ fft_gpu_plan_t fft_gpu_plan_1d_ex_hip(int n, int batch, fft_direction dir, fft_p
  * Execute with fft_gpu_execute(_ptr/_async); in == out allowed.  fft_gpu_plan_2d_hip replaces the stub gpu/fft_gpu.c:377-385. */
 fft_gpu_plan_t fft_gpu_plan_2d_hip(int rows, int cols, fft_direction dir);
 fft_gpu_plan_t fft_gpu_plan_2d_ex_hip(int rows, int cols, int n_matrices, fft_direction dir, fft_precision_t prec);
+/* 3D complex transforms of `n_volumes` row-major [depth][rows][cols] volumes (cols fastest, contiguous): numpy's fftn / ifftn over the
+ * last three axes; the inverse is scaled once by 1 / (depth * rows * cols).  Execute with fft_gpu_execute(_ptr/_async); in == out allowed.
+ * Where rows and cols are powers of two >= 8 and a plane fits the device's LDS together with a register prefetch of the next (on the MI355X
+ * planes of up to 8192 values in fp32 and 4096 in fp64: every plane from 8 x 8 to 64 x 64 in both precisions) an execute is two launches and two HBM round trips: one kernel transforms whole
+ * contiguous planes inside LDS, the depth transforms then run in place as strided column passes (depth a power of two) or on the
+ * transposed volume in a workspace of the plan's own.  Every other shape >= 1 x 1 x 1, and FFT_GPU_OPT_NO_FUSION: the 2D plan on the
+ * planes, then the same depth step.  AUTO only; 7-smooth lengths follow fft_gpu_set_smooth_policy_hip as fft_gpu_plan_2d_ex_hip's do.
+ * fft_gpu_plan_info_hip: n = cols, batch = n_volumes, factors = {cols, rows, depth}, fused = 1 where the plane kernel runs,
+ * n_passes = launches per execute (a chirp-z depth counts as an estimate).
+ * NULL: a size < 1, depth * rows * cols > 2^30, rows * cols * n_volumes or depth * n_volumes * max(rows, cols) > 2^31 - 1, a failed allocation. */
+fft_gpu_plan_t fft_gpu_plan_3d_hip(int depth, int rows, int cols, int n_volumes, fft_direction dir, fft_precision_t prec);
 /* real-input forward / real-output inverse 1D transforms (reference stubs algorithms/auto/fft_auto.c:391-409): r2c reads
  * [batch][n] reals and writes [batch][n/2 + 1] complex bins; c2r the reverse, scaled by 1/n.  Execute with fft_gpu_execute_ptr. */
 fft_gpu_plan_t fft_gpu_plan_r2c_1d_hip(int n, int batch, fft_precision_t prec);
